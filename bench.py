@@ -1,8 +1,15 @@
 """bench.py — ECDSA verifies/s of the MI355X signature hot path (BASELINE.json metric).
 
     python bench.py [--gpus N --steps K --warmup W --config c2|c3|c4|c5|c5t --n UNITS_PER_GPU]
+                    [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
              --master-port P bench.py --gpus N ...)
+
+A plain run stages the inputs, warms up, times the K steps and prints the headline line (metric,
+value, unit, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step computed
+(DIR/<name>.npy, float32; the inputs depend only on the arguments, so two builds can be compared
+output for output).  Everything under "Also reported" below, the validity checks and the side
+legs run only with --full.
 
 Default workload (BASELINE.json configs[1]): n synthetic P2WPKH spends per GPU
 (default 1,000,000), inputs resident in HBM (staged by the engine's own first-round interpreter
@@ -22,13 +29,13 @@ Other configs (run explicitly, results committed under profiles/
       (8M per GPU = the per-GPU shard of the 64M-tuple node batch); a step is the ECDSA kernels.
   c5  BIP340 rows (GPU-signed + the 15 BIP340 vectors tiled), a step is the Schnorr kernels.
 
-Also reported:
+Also reported (--full):
   roofline      the signature kernels against the measured v_mad_u64_u32 issue rate (int-ALU
                 bound: MFMA is deliberately unused; SURVEY.md §8d W = 2,257 modmuls = 144,448
                 32x32->64 partial products per ECDSA verify; DESIGN.md §3 for BIP340), kernel time
                 from HIP events on the launch stream
   cpu_baseline  the REFERENCE (oracle/_ref: Bitcoin Core v0.21 libbitcoinconsensus + libsecp256k1
-                built from /root/reference) on a bounded sample of the same inputs, std::thread
+                built by oracle/Makefile) on a bounded sample of the same inputs, std::thread
                 pool over the host cores (rank 0, N = 1 only)
 """
 import argparse
@@ -52,10 +59,30 @@ ECDSA_KERNELS = ("ecdsa (batch_sinv + twist_keyq + twist_ladder_g + twist_fin<ec
 SCHNORR_KERNELS = ("schnorr (schnorr_tladder: prep + ladder fused, + twist_fin<bip340>; "
                    "no lift_x square root)")
 CPU_PASSES = 3                    # timed passes of the CPU baseline (median), after 1 warm-up
+DUMP_BYTES = 60_000_000           # --dump-outputs: all files of one rank together stay below this
+DUMP_SEED = 0xD0A7                # ... and the rows of a larger output are sampled from this seed
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: every array of `arrays` (name -> rows of small integers) as
+    DIR/<name>.npy in float32 (DIR/<name>.rank<r>.npy in a multi-rank run).  An array above its
+    share of DUMP_BYTES is cut to a fixed sample of its rows (sorted indices drawn from
+    DUMP_SEED, so the same rows in every run and every build)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays)) - 4096  # (4096: the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        row = 4 * max(1, a[0].size if len(a) else 1)
+        if len(a) * row > share:
+            keep = np.random.default_rng(DUMP_SEED).choice(len(a), share // row, replace=False)
+            a = a[np.sort(keep)]
+        suffix = f".rank{rank}" if world > 1 else ""
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a.astype(np.float32))
 
 
 def _reference():
@@ -384,6 +411,12 @@ class C2:
     def valid(self):
         return sum(self.wl.verdicts())
 
+    def outputs(self):
+        """What the last step left for its caller: one verdict and one sighash per tuple row."""
+        import numpy as np
+        return {"verdicts": np.frombuffer(self.wl.verdicts(), np.uint8),
+                "sighashes": np.frombuffer(self.wl.msgs(), np.uint8).reshape(-1, 32)}
+
     def item_verdicts(self):
         v = self.wl.verdicts()
         out = bytearray(self.n)
@@ -530,10 +563,15 @@ class C3(C2):
         self.shape = self.wl.shape()
         self.units = self.wl.n           # inputs
         self.n = self.wl.n
-        self._valid = 0
+        self._valid, self._ret = 0, b""
 
     def step(self, sp):
-        self._valid, _ = self.wl.verify_batch()
+        self._valid, self._ret = self.wl.verify_batch()
+
+    def outputs(self):
+        """The last verify_batch call's per-input results."""
+        import numpy as np
+        return {"verdicts": np.frombuffer(self._ret, np.uint8)}
 
     def item_verdicts(self):
         return self._ret
@@ -602,6 +640,10 @@ class TupleJob:
         h = self.ts.host()
         self.mismatch_vs_construction = int((v != h["expect"]).sum())
         return int(v.sum())
+
+    def outputs(self):
+        import numpy as np
+        return {"verdicts": np.frombuffer(self.ts.verdicts(), np.uint8)}
 
     def item_verdicts(self):
         return self.ts.verdicts()
@@ -835,6 +877,9 @@ class C5T:
         self.step(None)
         return int((self.ret == 1).sum())
 
+    def outputs(self):
+        return {"ret": self.ret, "serror": self.err}
+
     def item_verdicts(self):
         return bytes((self.ret == 1).astype("uint8"))
 
@@ -971,6 +1016,14 @@ def main():
     ap.add_argument("--n", type=int, default=None,
                     help="units per GPU: inputs (c2), transactions (c3), tuples (c4, c5)")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as "
+                         "DIR/<name>.npy (float32; a fixed sample of the rows of a large output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: validity "
+                         "counts, sustained window, roofline and per-kernel times, CPU baseline, "
+                         "drop-in / single-call legs, the C3 / C4 side legs (the options below "
+                         "only shape such a run)")
     ap.add_argument("--cpu-sample", type=int, default=None)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
@@ -1014,21 +1067,23 @@ def main():
     else:
         job = TupleJob(B, n, seed, dev, args.config, first=first, total=total)
     log(f"[rank {rank}] staged {args.config} x{n} in {time.time() - t0:.1f}s")
-    probe = os.environ.get("BCC_BENCH_E2E_PROBE") and args.config == "c4"
+    full = args.full
+    extra = full and not args.no_extra
+    probe = full and os.environ.get("BCC_BENCH_E2E_PROBE") and args.config == "c4"
 
     def e2e_probe(where):  # (diagnostics: the C4 drop-in leg at points of the run)
         if probe:
             log(f"[e2e probe] {where}: {job.end_to_end(job.ts.host())['calls_ms']}")
     e2e_probe("after staging")
     side = None
-    if args.config == "c2" and os.environ.get("BCC_BENCH_DROPIN_EARLY") and not args.no_extra:
+    if args.config == "c2" and os.environ.get("BCC_BENCH_DROPIN_EARLY") and extra:
         job.wl.verify_batch()  # (diagnostics: the drop-in's host state allocated first)
-    if args.config == "c2" and world == 1 and not args.no_extra and not args.no_side:
+    if args.config == "c2" and world == 1 and extra and not args.no_side:
         side = SideLegs(B, dev, args.side_c4)
         log(f"[rank {rank}] side legs (C3, C4 x{args.side_c4}) set up in {side.setup_s:.1f}s")
     # (the same for the C2 drop-in leg measured neutral within the boxes' noise: not done)
     early_alloc = not os.environ.get("BCC_BENCH_NO_EARLY_ALLOC")  # (A/B of the note below)
-    if args.config == "c4" and not args.no_extra and early_alloc:
+    if args.config == "c4" and extra and early_alloc:
         # one untimed drop-in call now, so that its pinned round images, device batches and
         # scratch are allocated beside the staged set rather than after the whole run: allocated
         # last, the same calls ran ~40 % slower on the device (profiles/r05/c4_der/
@@ -1045,7 +1100,7 @@ def main():
     for _ in range(args.warmup):
         job.step(sp)
     torch.cuda.synchronize()
-    n_valid = job.valid()
+    n_valid = job.valid() if full else 0
     e2e_probe("after warmup + valid")
 
     def barrier():
@@ -1061,6 +1116,25 @@ def main():
     barrier()
     elapsed = time.perf_counter() - ts
     elapsed, n_valid_all = aggregate(elapsed, n_valid, world)
+    value = job.units * world * args.steps / elapsed
+    # the headline line: all a plain run reports
+    out = {
+        "metric": METRIC, "value": value, "unit": job.unit, "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+        "data": job.data,
+        "config": job.config(world),
+    }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, job.outputs(), rank, world)
+    if not full:
+        if rank == 0:
+            out["source_hash"] = B.source_hash()
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # sustained window: the same step back to back for >= --sustain-s seconds on every rank
     # (outside the K timed steps; a driver-side GPU-busy sampler sees a multi-second busy run)
@@ -1087,7 +1161,7 @@ def main():
     # calls bitcoinconsensus_verify_batch on its own slice from host buffers at the same time,
     # barrier-bracketed, max over ranks; reported beside value (host pass + H2D included)
     per_rank = None
-    if args.config == "c2" and not args.no_extra:
+    if args.config == "c2" and extra:
         job.wl.verify_batch()  # warm this rank's host / device state
         best = None
         for _ in range(2):
@@ -1112,8 +1186,6 @@ def main():
     e2e_probe("after kernel_times")
     sig_units = job.shape["tuples"] if args.config in ("c2", "c3", "c5t") else job.units
 
-    total = job.units * world * args.steps
-    value = total / elapsed
     if rank == 0:
         # peak: the v_mad_u64_u32 issue limit at the spec clock (MI355X_MICROARCH.md: 2400 MHz max;
         # a wave64 v_mad_u64_u32 occupies its SIMD 4 cycles: 16 lanes/clk/SIMD x 4 SIMDs x CUs);
@@ -1165,18 +1237,9 @@ def main():
             default_sample = {"c2": 200_000, "c3": 100_000, "c4": 400_000, "c5": 400_000,
                               "c5t": 200_000}
             cpu = job.cpu(args.cpu_sample or default_sample[args.config])
-        out = {
-            "metric": METRIC, "value": value, "unit": job.unit, "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-            "data": job.data,
-            "config": job.config(world),
-            "roofline": roof,
-            "cpu_baseline": cpu,
-        }
+        out.update(roofline=roof, cpu_baseline=cpu)
         e2e_probe("before extra")
-        if not args.no_extra:
+        if extra:
             out.update(job.extra(sighash_ms))
         if sustained:
             out["sustained"] = sustained

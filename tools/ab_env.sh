@@ -10,7 +10,7 @@ for i in $(seq 1 $R); do
   for e in "$@"; do
     k=$((k+1)); [ "$e" = "-" ] && e=""
     f=$O/ab_${C}_${k}_$i
-    env $e timeout -k 10 300 python bench.py --config $C --steps 20 --warmup 10 --no-cpu > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+    env $e timeout -k 10 300 python bench.py --full --config $C --steps 20 --warmup 10 --no-cpu > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
     python3 -c "import json; d=json.load(open('$f.json')); r=d['roofline']; b=d.get('batch_stats',{}); print('$C', '[$e]', $i, round(d['value']/1e6,3), 'ms', round(d['ms_per_step'],3), 'stage', round(r.get('per_launch',{}).get('avg_ms',0),3), 'frac', round(r['frac'],4), 'valid', d['verdicts_valid'], 'gpu_ms', round(1e3*b.get('gpu_seconds',0),3), 'host_ms', round(1e3*b.get('host_seconds',0),3))"
   done
 done

@@ -8,7 +8,7 @@ i=0
 for rep in $(seq 1 $R); do
   for s in "$@"; do
     i=$((i + 1))
-    timeout -k 10 300 env $s python3 bench.py $A > $O/b_$i.json 2> $O/b_$i.err || { tail -5 $O/b_$i.err; exit 1; }
+    timeout -k 10 300 env $s python3 bench.py --full $A > $O/b_$i.json 2> $O/b_$i.err || { tail -5 $O/b_$i.err; exit 1; }
     python3 - "$s" $O/b_$i.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1]); r = d["roofline"]

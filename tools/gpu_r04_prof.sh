@@ -11,6 +11,6 @@ bash tools/isa/pmc_decomp.sh $T/isa > $O/isa.log 2>&1 || { tail -20 $O/isa.log; 
 FULL=1 bash tools/profile_c2.sh $T/prof > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 3; }
 tail -15 $O/prof.log
 for c in c3 c5 c5t; do
-  timeout -k 10 400 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 4; }
+  timeout -k 10 400 python bench.py --full --config $c > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 4; }
   python3 -c "import json; d=json.load(open('$O/bench_$c.json')); print('$c', d['value']/1e6, d['ms_per_step'], d['roofline']['frac'])"
 done

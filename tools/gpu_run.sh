@@ -4,7 +4,7 @@
 #   tools/gpu_run.sh TAG STEP...
 #   STEP: tests[=PYTEST_K_EXPR]   pytest -m gpu (optionally -k EXPR)        -> pytest_gpu.log
 #         smoke                   __graft_entry__.smoke()                  -> smoke.log
-#         bench[=ARGS]            python bench.py ARGS (',' for spaces)    -> bench_N.json / .err
+#         bench[=ARGS]            python bench.py --full ARGS (',' for spaces)    -> bench_N.json / .err
 #         dropin[=N,CALLS]        tools/dropin_e2e.py (drop-in alone)      -> dropin.txt
 #         prof=CONFIG             tools/profile_c2.sh-style trace of one bench config
 set -o pipefail
@@ -27,7 +27,7 @@ for step in "$@"; do
         || { tail -20 $O/smoke.log; exit 2; }
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py ${arg//,/ } > $O/bench_$i.json 2> $O/bench_$i.err \
+      timeout -k 10 600 python bench.py --full ${arg//,/ } > $O/bench_$i.json 2> $O/bench_$i.err \
         || { tail -20 $O/bench_$i.err; exit 3; }
       python3 tools/bench_summary.py $O/bench_$i.json ;;
     dropin)
@@ -38,7 +38,7 @@ for step in "$@"; do
     prof)
       mkdir -p $O/prof_$arg
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$arg -o run -- \
-        python3 bench.py --config $arg --no-extra --no-cpu --steps 10 --warmup 3 --sustain-s 0 \
+        python3 bench.py --full --config $arg --no-extra --no-cpu --steps 10 --warmup 3 --sustain-s 0 \
         > $O/prof_$arg/bench.json 2> $O/prof_$arg/bench.err || { tail -20 $O/prof_$arg/bench.err; exit 5; } ;;
     *) echo "unknown step $step"; exit 9 ;;
   esac

@@ -9,9 +9,9 @@ O=gpurun_out/$T
 mkdir -p $O
 FULL=1 bash tools/profile_c2.sh $T > $O/profile.txt 2>&1 || { tail -20 $O/profile.txt; exit 1; }
 tail -14 $O/profile.txt
-timeout -k 10 400 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 2; }
+timeout -k 10 400 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 2; }
 for c in c3 c4 c5 c5t; do
-  timeout -k 10 400 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 3; }
+  timeout -k 10 400 python bench.py --full --config $c > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 3; }
 done
 python3 - "$O" <<'PY'
 import json, sys

@@ -55,7 +55,7 @@ def main(d):
         if "fetch_size_bytes_per_launch" in e:
             e["fetch_bytes_x2_per_launch"] = 2 * e["fetch_size_bytes_per_launch"]
     # per signature stage = all launches of one run_ecdsa / schnorr call.  The PMC passes run
-    # bench.py --steps 1 --warmup 0: one timed step + 3 HIP-event timing repetitions = 4 stages,
+    # bench.py --full --steps 1 --warmup 0: one timed step + 3 HIP-event timing repetitions = 4 stages,
     # plus, for the C2 line (which carries drop_in_end_to_end), 3 drop-in verify_batch runs over
     # the same inputs = 7.  A stage may launch a kernel once per lane chunk (C4 at 8M, C5 at 16M).
     stages = {"ecdsa": ["batch_sinv_kernel", "ecdsa_tprep_kernel", "twist_keyq_kernel", "twist_keyq2_kernel",
@@ -83,7 +83,7 @@ def main(d):
         wb = sum(K[k].get("write_size_bytes_total", 0) for k in ks if k in K) / n_stage
         out.setdefault("stages", {})[st] = dict(executions=n_stage, fetch_bytes=fb, fetch_bytes_x2=2 * fb,
                                                write_bytes=wb, traffic_bytes=2 * fb + wb)
-        # per stage execution from the PMC launches (bench.py --no-extra runs: every stage full-size)
+        # per stage execution from the PMC launches (bench.py --full --no-extra runs: every stage full-size)
         fl = sum(K[k].get("fetch_size_bytes_total", 0) for k in ks if k in K) / n_stage
         wl = sum(K[k].get("write_size_bytes_total", 0) for k in ks if k in K) / n_stage
         out["stages"][st].update(per_launch_fetch_bytes_x2=2 * fl, per_launch_write_bytes=wl,

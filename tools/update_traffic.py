@@ -3,7 +3,7 @@
     python3 tools/update_traffic.py profiles/r03/r03y/c2/summary.json c2 1000000
 
 traffic = HBM bytes per signature stage (FETCH_SIZE x 2 + WRITE_SIZE of the stage's kernels over
-the run / the stage executions; bench.py --no-extra runs, so there are no other launches), the form bench.py
+the run / the stage executions; bench.py --full --no-extra runs, so there are no other launches), the form bench.py
 reads into roofline.traffic (it checks units and the kernel description)."""
 import json
 import os
@@ -25,7 +25,7 @@ def main(summary, config, units):
     e.update(units=units, traffic_bytes=st["traffic_bytes"],
              fetch_bytes_x2=st["fetch_bytes_x2"], write_bytes=st["write_bytes"],
              source=f"{os.path.relpath(summary, ROOT)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes "
-                    f"over bench.py --no-extra, {st['executions']} stage executions of "
+                    f"over bench.py --full --no-extra, {st['executions']} stage executions of "
                     f"{', '.join(st['kernels'])}; FETCH doubled per MI355X_MICROARCH.md)",
              kernel=bench.ECDSA_KERNELS if config in ("c2", "c3", "c4") else bench.SCHNORR_KERNELS)
     e.pop("instruction_mix", None)
