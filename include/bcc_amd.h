@@ -70,7 +70,8 @@ typedef struct bcc_taproot_check {
     int sigversion;                     /* BCC_SIGVERSION_* */
     const unsigned char* annex;         /* the annex witness element incl. 0x50, NULL: none */
     unsigned int annex_len;
-    const unsigned char* tapleaf_hash32; /* TAPSCRIPT only (execdata.m_tapleaf_hash) */
+    const unsigned char* tapleaf_hash32; /* TAPSCRIPT only (execdata.m_tapleaf_hash); it is what
+                                          * bcc_taproot_commit_batch writes to tapleaf_out */
     uint32_t codeseparator_pos;         /* TAPSCRIPT only (0xFFFFFFFF: none executed) */
 } bcc_taproot_check;
 /* script_error.h:73-75 values written to serror_out */
@@ -87,6 +88,57 @@ typedef struct bcc_taproot_check {
  * arguments or a device failure (then no output is meaningful). */
 int bcc_taproot_verify_batch(const bcc_taproot_check* items, size_t n, int* ret_out,
                              int* serror_out, unsigned char* sighash_out, int device);
+
+/* ---- BIP341 script-path commitment ---------------------------------------------------------------
+ * Replaces the commitment check of a script-path spend in VerifyWitnessProgram
+ * (depend/bitcoin/src/script/interpreter.cpp:1909-1914): the control-size rule, then
+ * VerifyTaprootCommitment (:1834-1853) = the TapLeaf hash of the script, one TapBranch hash per
+ * 32-byte node of the control block, the TapTweak hash and XOnlyPubKey::CheckPayToContract
+ * (pubkey.cpp:184-189): lift_x(p) + t G == (q, parity).  All hashes and the curve check run on the
+ * GPU.  The caller has removed the annex; any leaf version is accepted (leaf version =
+ * control[0] & 0xfe, parity = control[0] & 1, p = control[1..33)). */
+typedef struct bcc_taproot_commit {
+    const unsigned char* control;   /* the control block witness element */
+    unsigned int control_len;
+    const unsigned char* script;    /* the leaf script (may be empty; NULL only with script_len 0) */
+    unsigned int script_len;
+    const unsigned char* program32; /* the 32-byte v1 witness program q */
+} bcc_taproot_commit;
+/* script_error.h values written to serror_out */
+#define BCC_SCRIPT_ERR_WITNESS_PROGRAM_MISMATCH 39
+#define BCC_SCRIPT_ERR_TAPROOT_WRONG_CONTROL_SIZE 47
+/* Per item: ret_out[i] = 1, serror_out[i] = 0 when the commitment holds; ret 0 / serror 47 when
+ * control_len < 33, control_len > 33 + 32 * 128 or (control_len - 33) % 32 != 0 (nothing is hashed
+ * for such an item); ret 0 / serror 39 when VerifyTaprootCommitment is false.  tapleaf_out
+ * (optional, 32 bytes per item): the TapLeaf hash of every item whose control size is valid,
+ * whether or not the commitment holds, else zeros; a caller hands it on as
+ * bcc_taproot_check.tapleaf_hash32.  Synchronous on `device`, or for device = -1 spread in
+ * contiguous ranges over the bcc_set_devices() GPUs; batches of at most
+ * bcc_set_host_small_round() items run the same lane code on the host.  Results never depend on
+ * the device set, the round cut or the thread count.  Returns 0 (also for n == 0), or -1 for null
+ * arrays, an item with a null control, program32 or (with script_len > 0) script: nothing is
+ * verified then; or -1 on a device failure (then no output is meaningful). */
+int bcc_taproot_commit_batch(const bcc_taproot_commit* items, size_t n, int* ret_out,
+                             int* serror_out, unsigned char* tapleaf_out, int device);
+
+/* The layer below (the role mi_schnorr_verify_tuples has for signatures): n rows of the tweaked
+ * key q, the parity byte, the internal key p and the tweak t (32-byte big-endian strings).
+ * verdict[i] = 1 iff secp256k1_xonly_pubkey_parse(internal32_i) succeeds and
+ * secp256k1_xonly_pubkey_tweak_add_check(tweaked32_i, parity_i, ., tweak32_i) returns 1
+ * (secp256k1/src/modules/extrakeys/main_impl.h:21-41, 109-129); a parity byte other than 0 or 1
+ * gives 0.  Synchronous on `device` (-1: spread over the bcc_set_devices() GPUs); at most
+ * bcc_set_host_small_round() rows run on the host.  Returns 0, -1 for null arrays, or a HIP error
+ * code on a device failure. */
+int mi_xonly_tweak_check_tuples(const uint8_t* tweaked32, const uint8_t* parity,
+                                const uint8_t* internal32, const uint8_t* tweak32,
+                                uint8_t* verdict, size_t n, int device);
+
+/* Event times in milliseconds of the commitment kernels during the calling thread's last
+ * bcc_taproot_commit_batch / mi_xonly_tweak_check_tuples call on one device, summed over its
+ * rounds: ms3[0] the hashing kernel, ms3[1] the curve kernel (lift, comb, addition), ms3[2] the
+ * batched inversion and comparison.  Zeros unless BCC_COMMIT_TIMING=1 was in the environment when
+ * the library was loaded (measurement tools: tools/commit_bench.py). */
+void bcc_commit_last_kernel_ms(double* ms3);
 
 /* ---- tuple level with the CPubKey front end ---------------------------------------------------
  * verdict[i] = CPubKey(pub_i).Verify(msg_i, sig_i) (depend/bitcoin/src/pubkey.cpp:191-207) for n

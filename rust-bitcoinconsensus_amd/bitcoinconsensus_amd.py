@@ -92,6 +92,10 @@ def lib():
         L.bcc_taproot_verify_batch.argtypes = [ctypes.POINTER(TaprootCheck), sz,
                                                ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int), vp, ctypes.c_int]
+        L.bcc_taproot_commit_batch.argtypes = [ctypes.POINTER(TaprootCommit), sz,
+                                               ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(ctypes.c_int), vp, ctypes.c_int]
+        L.mi_xonly_tweak_check_tuples.argtypes = [u8p, u8p, u8p, u8p, u8p, sz, ctypes.c_int]
         L.bcc_debug_scratch_cap_lanes.argtypes = [sz]
         _bind_consensus(L)
         L.bcc_source_hash.restype = ctypes.c_char_p
@@ -671,6 +675,68 @@ def taproot_verify_batch(checks, device=0, sighashes=False, library=None):
     if sighashes:
         return out, [hs.raw[32 * i: 32 * i + 32] for i in range(n)]
     return out
+
+
+SCRIPT_ERR_WITNESS_PROGRAM_MISMATCH = 39
+SCRIPT_ERR_TAPROOT_WRONG_CONTROL_SIZE = 47
+
+
+class TaprootCommit(ctypes.Structure):
+    """include/bcc_amd.h bcc_taproot_commit."""
+    _fields_ = [("control", ctypes.c_char_p), ("control_len", ctypes.c_uint),
+                ("script", ctypes.c_char_p), ("script_len", ctypes.c_uint),
+                ("program32", ctypes.c_char_p)]
+
+
+def taproot_commit_batch(items, device=0, tapleaf=False, library=None):
+    """The script-path commitment check of VerifyWitnessProgram for each item
+    (depend/bitcoin/src/script/interpreter.cpp:1909-1914 with VerifyTaprootCommitment, :1834-1853;
+    include/bcc_amd.h bcc_taproot_commit_batch).  An item is a dict with keys control (the control
+    block witness element), script (the leaf script) and program (the 32-byte witness program).
+    Returns [(ret, serror)]: (1, 0), (0, SCRIPT_ERR_WITNESS_PROGRAM_MISMATCH) or
+    (0, SCRIPT_ERR_TAPROOT_WRONG_CONTROL_SIZE); plus the 32-byte TapLeaf hashes (zeros for a wrong
+    control size) when tapleaf=True: the value taproot_verify_batch takes as `tapleaf`."""
+    n = len(items)
+    arr = (TaprootCommit * max(n, 1))()
+    keep = []
+    for i, c in enumerate(items):
+        control, script, program = bytes(c["control"]), bytes(c["script"]), bytes(c["program"])
+        assert len(program) == 32
+        keep.append((control, script, program))
+        arr[i] = TaprootCommit(control, len(control), script, len(script), program)
+    ret = (ctypes.c_int * max(n, 1))()
+    err = (ctypes.c_int * max(n, 1))()
+    hs = ctypes.create_string_buffer(32 * max(n, 1)) if tapleaf else None
+    L = library if library is not None else lib()
+    rc = L.bcc_taproot_commit_batch(arr, n, ret, err, hs, device)
+    if rc != 0:
+        raise RuntimeError(f"bcc_taproot_commit_batch failed: {rc}")
+    out = [(ret[i], err[i]) for i in range(n)]
+    if tapleaf:
+        return out, [hs.raw[32 * i: 32 * i + 32] for i in range(n)]
+    return out
+
+
+def xonly_tweak_check_tuples(tweaked32, parity, internal32, tweak32, device=0):
+    """The curve half of the commitment check as a tuple ABI: n rows as concatenated byte strings
+    (tweaked key q, one parity byte, internal key p, tweak t) -> bytes of verdicts.  Row semantics
+    of secp256k1_xonly_pubkey_parse(p) + secp256k1_xonly_pubkey_tweak_add_check(q, parity, p, t)."""
+    n = len(parity)
+    assert len(tweaked32) == 32 * n and len(internal32) == 32 * n and len(tweak32) == 32 * n
+    out = ctypes.create_string_buffer(max(n, 1))
+    rc = lib().mi_xonly_tweak_check_tuples(bytes(tweaked32), bytes(parity), bytes(internal32),
+                                           bytes(tweak32), out, n, device)
+    if rc != 0:
+        raise RuntimeError(f"mi_xonly_tweak_check_tuples failed: {rc}")
+    return out.raw[:n]
+
+
+def commit_last_kernel_ms():
+    """bcc_commit_last_kernel_ms: (hash, curve, inversion + compare) kernel event times in ms of
+    the calling thread's last commitment call; zeros unless BCC_COMMIT_TIMING=1 was set at load."""
+    ms = (ctypes.c_double * 3)()
+    lib().bcc_commit_last_kernel_ms(ms)
+    return tuple(ms)
 
 
 class TupleSet:

@@ -1167,20 +1167,21 @@ struct ThreadCtx {
         if (dbuf) (void)hipFree(dbuf);
         if (hbuf) (void)hipHostFree(hbuf);
     }
-    int reserve(size_t bytes) {
-        if (bytes > dcap) {
+    int reserve(size_t bytes) { return reserve(bytes, bytes); }
+    int reserve(size_t dbytes, size_t hbytes) {
+        if (dbytes > dcap) {
             if (dbuf) BCC_HIP_TRY(hipFree(dbuf));
             dbuf = nullptr;
             dcap = 0;
-            BCC_HIP_TRY(hipMalloc(&dbuf, bytes));
-            dcap = bytes;
+            BCC_HIP_TRY(hipMalloc(&dbuf, dbytes));
+            dcap = dbytes;
         }
-        if (bytes > hcap) {
+        if (hbytes > hcap) {
             if (hbuf) BCC_HIP_TRY(hipHostFree(hbuf));
             hbuf = nullptr;
             hcap = 0;
-            BCC_HIP_TRY(hipHostMalloc(&hbuf, bytes, hipHostMallocDefault));
-            hcap = bytes;
+            BCC_HIP_TRY(hipHostMalloc(&hbuf, hbytes, hipHostMallocDefault));
+            hcap = hbytes;
         }
         return 0;
     }
@@ -1204,6 +1205,25 @@ static int thread_ctx(int device, ThreadCtx** out) {
     }
     *out = ctx[device].get();
     return 0;
+}
+
+// The same context for the commitment entries (taproot_commit.hip): the calling thread's stream
+// on `device` (made current) and its two buffers grown to at least dbytes / hbytes.
+int tuple_thread_buffers(int device, size_t dbytes, size_t hbytes, void** dbuf, void** hbuf,
+                         void** stream) {
+    BCC_HIP_TRY(hipSetDevice(device));
+    ThreadCtx* ctx = nullptr;
+    if (int e = thread_ctx(device, &ctx)) return e;
+    if (int e = ctx->reserve(dbytes, hbytes)) return e;
+    *dbuf = ctx->dbuf;
+    *hbuf = ctx->hbuf;
+    *stream = ctx->stream;
+    return 0;
+}
+
+// The current device's comb tables (device_tables) for kernels outside this file.
+int comb_device_tables(int* dev, const uint32_t** gcomb, int* cus) {
+    return device_tables(dev, gcomb, cus);
 }
 
 }  // namespace bcc

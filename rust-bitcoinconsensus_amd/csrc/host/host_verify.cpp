@@ -220,6 +220,9 @@ int host_verify_parts(const SighashJobs* const* jobs, const TupleRows* const* ro
     return 0;
 }
 
+// The host copy of the comb tables for lane code outside this file (taproot_commit.hip).
+const void* host_comb_tables() { return comb_tables(); }
+
 namespace {
 std::atomic<size_t> g_small_round{[] {
     const char* e = getenv("BCC_HOST_SMALL_ROUND");

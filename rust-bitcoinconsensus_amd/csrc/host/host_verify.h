@@ -28,6 +28,10 @@ void apply_key_hashes(const TupleRows& R, uint8_t* verdict);
 int host_verify_parts(const SighashJobs* const* jobs, const TupleRows* const* rows, size_t P,
                       uint8_t* verdict, unsigned threads);
 
+// The fixed-base comb tables on the host (ecdsa_twist.h GCombArray layout, an array of fe), built
+// on first use.
+const void* host_comb_tables();
+
 size_t host_small_round();     // bcc_set_host_small_round (0: every round on the GPU)
 bool host_fallback_enabled();  // bcc_set_device_failure_policy == BCC_DEVICE_FAILURE_HOST
 void note_host_fallback();     // counts bcc_host_fallback_rounds

@@ -707,6 +707,15 @@ bool direct_upload();
 void release_device_thread_state();
 void release_tuple_thread_state();
 
+// The tuple-path context of the calling thread on `device` (ecdsa_verify.hip ThreadCtx), shared
+// with the commitment entries (taproot_commit.hip): makes the device current and returns the
+// thread's stream, its device buffer grown to dbytes and its page-locked buffer grown to hbytes.
+// The entries that use it are synchronous, so the buffers hold nothing between calls.
+int tuple_thread_buffers(int device, size_t dbytes, size_t hbytes, void** dbuf, void** hbuf,
+                         void** stream);
+// The current device's fixed-base comb tables (ecdsa_twist.h layout) and CU count.
+int comb_device_tables(int* dev, const uint32_t** gcomb, int* cus);
+
 // One-shot helper: stage + run + fetch on `device` (synchronous).
 // *stage_seconds (optional) receives the host -> HBM staging time.
 int gpu_verify_batch(int device, const SighashJobs& jobs, const TupleRows& rows, uint8_t* verdict,
