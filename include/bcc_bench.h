@@ -159,6 +159,18 @@ int mi_primbench(int prim, int iters, int warm, double* cycles, double* ms);
  * Results are weak (< 2^256) except 8-11. */
 int mi_fe_selftest(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n);
 
+/* ---- scalar self-test (tests only): one device mod-n operation over n operand pairs ---------
+ * a, b, out, out2: n x 8 little-endian u32 limbs.  op: 0 sc_mul (any 256-bit operands), 1 sc_sqr,
+ * 2 sc_add (a, b < n), 3 sc_neg (a < n), 4 / 5 sc_mul_shift_384 by the GLV constants g1 / g2,
+ * 6 sc_split_lambda (out = k1, out2 = k2), 7 fe_sqrt (weak a: out = the root normalized,
+ * out2[0] = the returned bool).  out2 is zero for ops 0-5.  -1 for an unknown op. */
+int mi_sc_selftest(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t* out2,
+                   size_t n);
+
+/* Compute units of `device` (tests size batches around the CU-derived launch thresholds);
+ * negative on error. */
+int mi_device_cus(int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,7 @@ def blib():
         L.mi_gen_pubkeys.argtypes = [u8p, sz, u8p, u8p, u8p, ctypes.c_int]
         L.mi_gen_sign.argtypes = [u8p, u8p, u8p, sz, u8p, u8p, u8p, ctypes.c_int]
         L.mi_gen_schnorr_sign.argtypes = [u8p, u8p, u8p, sz, u8p, u8p, u8p, ctypes.c_int]
+        L.mi_sc_selftest.argtypes = [ctypes.c_int, u32p, u32p, u32p, u32p, sz]
 
         _blib = L
     return _blib

@@ -164,6 +164,73 @@ extern "C" void lane_split(const unsigned char* k32, unsigned char* k1, unsigned
     fe_to_be_bytes(k2, t);
 }
 
+// Host twin of the device's mi_sc_selftest (csrc/bench/selftest.hip), same ops and layout: a, b,
+// out, out2 are n x 8 little-endian u32 limbs.  op: 0 sc_mul, 1 sc_sqr, 2 sc_add, 3 sc_neg,
+// 4 / 5 sc_mul_shift_384 by g1 / g2, 6 sc_split_lambda (out = k1, out2 = k2), 7 fe_sqrt (out = the
+// root normalized, out2[0] = the returned bool).
+extern "C" int lane_sc_selftest(int op, const uint32_t* a, const uint32_t* b, uint32_t* out,
+                                uint32_t* out2, size_t n) {
+    if (op < 0 || op > 7) return -1;
+    const u32 G1[8] = BCC_G1_LIMBS, G2[8] = BCC_G2_LIMBS;
+    for (size_t i = 0; i < n; i++) {
+        sc x, y, r, r2;
+        memcpy(x.v, a + 8 * i, 32);
+        memcpy(y.v, b + 8 * i, 32);
+        memset(r.v, 0, 32);
+        memset(r2.v, 0, 32);
+        switch (op) {
+            case 0: sc_mul(r, x, y); break;
+            case 1: sc_sqr(r, x); break;
+            case 2: sc_add(r, x, y); break;
+            case 3: sc_neg(r, x); break;
+            case 4: sc_mul_shift_384(r, x, G1); break;
+            case 5: sc_mul_shift_384(r, x, G2); break;
+            case 6: sc_split_lambda(r, r2, x); break;
+            default: {
+                fe fx, fr;
+                memcpy(fx.v, x.v, 32);
+                r2.v[0] = fe_sqrt(fr, fx) ? 1u : 0u;
+                fe_normalize(fr);
+                memcpy(r.v, fr.v, 32);
+            }
+        }
+        memcpy(out + 8 * i, r.v, 32);
+        memcpy(out2 + 8 * i, r2.v, 32);
+    }
+    return 0;
+}
+
+// The ladders' recodings as signed digits d = +-(2 idx + 1), lowest window first, plus the raw
+// table indices: digit_index over an odd 128-bit k (4 limbs; WQ-bit windows, 128 / WQ digits) and
+// comb_digit over an odd 256-bit u1 (8 limbs; WC-bit windows, CWIN digits).  Return the count.
+extern "C" int lane_recode_q(const uint32_t* k, int32_t* digits, uint32_t* idx) {
+    int cnt = 0;
+    for (int pos = 0; pos <= TOPQ; pos += WQ, cnt++) {
+        bool neg;
+        idx[cnt] = digit_index(k[0], k[1], k[2], k[3], pos, WQ, TOPQ, neg);
+        digits[cnt] = (neg ? -1 : 1) * (int32_t)(2 * idx[cnt] + 1);
+    }
+    return cnt;
+}
+extern "C" int lane_recode_comb(const uint32_t* u1, int32_t* digits, uint32_t* idx) {
+    TwistState st;
+    memcpy(st.k[2], u1, 16);
+    memcpy(st.k[3], u1 + 4, 16);
+    for (int win = 0; win < CWIN; win++) {
+        bool neg;
+        idx[win] = comb_digit(st, WC * win, neg);
+        digits[win] = (neg ? -1 : 1) * (int32_t)(2 * idx[win] + 1);
+    }
+    return CWIN;
+}
+extern "C" void lane_recode_params(int* out) {  // WQ, QTAB, WC, CTAB, CWIN
+    out[0] = WQ;
+    out[1] = QTAB;
+    out[2] = WC;
+    out[3] = CTAB;
+    out[4] = CWIN;
+}
+
 // the GPU lanes' safegcd inverse (csrc/modinv_device.h) on the CPU: r = a^-1 mod m, little-endian
 // 32-bit limbs, minv30 = m^-1 mod 2^30
 extern "C" void lane_mi30_inverse(const uint32_t* a, const uint32_t* m, uint32_t minv30,

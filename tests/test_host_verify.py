@@ -39,3 +39,20 @@ def test_host_verify_tuples_match_reference_fixtures():
     bad = [(t["cls"], i) for i, t in enumerate(ts) if out.raw[i] != t["verdict"]]
     assert not bad, bad[:10]
     assert len({t["cls"] for t in ts}) >= 15 and sum(t["verdict"] for t in ts) > 500
+
+
+def test_host_verify_structured_scalars():
+    """The structured-scalar fixture (chosen u1 / u2, tests/golden/structured_scalars.npz) through
+    the engine's host verification, rows and invalid twins."""
+    from fixtures import structured_scalars
+    L = load()
+    L.bcc_host_verify_tuples.argtypes = [ctypes.c_char_p] * 4 + [ctypes.c_char_p, ctypes.c_size_t,
+                                                                 ctypes.c_uint]
+    ts = structured_scalars()["ecdsa"]
+    pub = b"".join(bytes([t["pub"][0]]) + t["pub"][1:].ljust(64, b"\0") for t in ts)
+    msg, r32, s32 = (b"".join(t[k] for t in ts) for k in ("hash", "r32", "s32"))
+    out = ctypes.create_string_buffer(len(ts))
+    assert L.bcc_host_verify_tuples(pub, msg, r32, s32, out, len(ts), 4) == 0
+    bad = [(t["cls"], i) for i, t in enumerate(ts) if out.raw[i] != t["verdict"]]
+    assert not bad, (len(bad), bad[:10])
+    assert sum(t["verdict"] for t in ts) >= 3000

@@ -206,3 +206,17 @@ def test_commit_lane_code_vs_live_reference(host):
     got = host.tweak_check(ts, 16)
     bad = [(t[0], g) for t, g in zip(ts, got) if g != T.check(*t[1:])]
     assert not bad, bad[:10]
+
+
+def test_tweak_lane_code_structured_scalars(host):
+    """The comb's scalar families as tweaks (tests/golden/structured_scalars.npz: powers of two and
+    their neighbours, every window at the table's extremes, zero), rows and invalid twins, one
+    inversion per row and grouped."""
+    from fixtures import structured_scalars
+    rows = structured_scalars()["tweak"]
+    ts = [(t["cls"], t["q"], t["parity"], t["p"], t["t"]) for t in rows]
+    want = [t["verdict"] for t in rows]
+    assert sum(want) >= 2000 and want.count(0) >= 2000
+    for group in (None, 16):
+        got = host.tweak_check(ts, group)
+        assert [(group, t[0], g) for t, g, w in zip(ts, got, want) if g != w] == []
