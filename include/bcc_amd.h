@@ -121,6 +121,67 @@ typedef struct bcc_taproot_commit {
 int bcc_taproot_commit_batch(const bcc_taproot_commit* items, size_t n, int* ret_out,
                              int* serror_out, unsigned char* tapleaf_out, int device);
 
+/* ---- whole Taproot inputs --------------------------------------------------------------------
+ * Replaces VerifyScript (depend/bitcoin/src/script/interpreter.cpp:1937-2056) for an input that
+ * spends a native v1 witness program: VerifyWitnessProgram's v1 branch (:1889-1927) with the annex
+ * rule, the key path, the control-size rule, the commitment, the leaf version, and for leaf version
+ * 0xc0 the tapscript (ExecuteWitnessScript / EvalScript with SigVersion::TAPSCRIPT, :1794-1832,
+ * :431-1259, EvalChecksigTapscript :371-429).  The host interprets each tapscript once: a BIP342
+ * signature opcode with a non-empty signature either verifies or fails the whole script, so the
+ * pass assumes it verifies and queues the check.  A round's commitments (TapLeaf / TapBranch /
+ * TapTweak hashes, the curve check) and all its signature checks (key path and queued tapscript
+ * checks: SigMsg, TapSighash, BIP340) then run on the GPU in one stream; the TapLeaf hash reaches
+ * the signature hashes on the device. */
+typedef struct bcc_taproot_spend {
+    const unsigned char* tx;            /* serialized spending tx, exactly tx_len bytes */
+    unsigned int tx_len;
+    const unsigned char* spent_outputs; /* serialized std::vector<CTxOut>, one per input */
+    unsigned int spent_outputs_len;
+    unsigned int n_in;
+} bcc_taproot_spend;
+/* script_error.h values this entry adds to the ones above */
+#define BCC_SCRIPT_ERR_EVAL_FALSE 2
+#define BCC_SCRIPT_ERR_PUSH_SIZE 5
+#define BCC_SCRIPT_ERR_STACK_SIZE 7
+#define BCC_SCRIPT_ERR_BAD_OPCODE 15
+#define BCC_SCRIPT_ERR_PUBKEYTYPE 28
+#define BCC_SCRIPT_ERR_CLEANSTACK 29
+#define BCC_SCRIPT_ERR_WITNESS_PROGRAM_WITNESS_EMPTY 38
+#define BCC_SCRIPT_ERR_WITNESS_MALLEATED 40
+#define BCC_SCRIPT_ERR_TAPSCRIPT_VALIDATION_WEIGHT 48
+#define BCC_SCRIPT_ERR_TAPSCRIPT_CHECKMULTISIG 49
+#define BCC_SCRIPT_ERR_TAPSCRIPT_MINIMALIF 50
+/* Per item, ret_out[i] / serror_out[i] are what VerifyScript(tx.vin[n_in].scriptSig,
+ * spent_outputs[n_in].scriptPubKey, &witness, flags, checker, &serror) returns and writes, with
+ * flags = P2SH | DERSIG | NULLDUMMY | CHECKLOCKTIMEVERIFY | CHECKSEQUENCEVERIFY | WITNESS | TAPROOT
+ * (0xE15 | 1 << 17) and the checker's PrecomputedTransactionData initialised with the spent
+ * outputs: 1 / 0 when the input verifies, else 0 and the script_error.h number (any ScriptError the
+ * interpreter can set, not only the ones defined here).  A spend's result is, in this order: the
+ * control-size error; the commitment mismatch; SCHNORR_SIG when a queued signature check fails;
+ * the interpreter's own result.  ret -1 / serror 1 where the reference checker cannot be built
+ * (of the conditions bcc_taproot_verify_batch documents: the tx does not deserialize to exactly
+ * tx_len bytes, the spent outputs do not parse or their count differs from the tx's inputs,
+ * n_in >= inputs; BIP341-readiness follows from the next condition whenever a signature check is
+ * reached), where the spent scriptPubKey is not exactly OP_1 0x20 <32 bytes> (this entry is for
+ * native v1 programs; everything else belongs to bitcoinconsensus_verify_batch), and where the
+ * result of a non-empty scriptSig depends on ECDSA checks of non-empty signatures, for which this
+ * entry has no lane: a scriptSig without such a check gives its own error or WITNESS_MALLEATED; one
+ * that meets exactly one is run with both verdicts and reported when both runs agree (a lone
+ * OP_CHECKSIG only pushes its verdict: WITNESS_MALLEATED either way); any other gets ret -1.
+ * Synchronous on `device`, or for device = -1 spread in contiguous ranges over the
+ * bcc_set_devices() GPUs; batches of at most bcc_set_host_small_round() items run the commitment
+ * lane code on the host.  Adjacent items with the same tx and spent_outputs pointers share the
+ * per-tx work.  Results never depend on the device set, the round cut or the thread count.
+ * Returns 0 (also for n == 0), -1 for null arrays or an item with a null tx or spent_outputs
+ * (nothing is verified then), or -1 on a device failure (then no output is meaningful; a failed
+ * device round is not retried on the host). */
+int bcc_taproot_spend_batch(const bcc_taproot_spend* items, size_t n, int* ret_out,
+                            int* serror_out, int device);
+/* Items per device round of bcc_taproot_spend_batch (0, the default: the engine's choice, 65,536).
+ * Rounds rotate over the Taproot contexts, so one round's upload runs beside the previous round's
+ * kernels.  For tests: a small value puts round boundaries inside a small batch.  Returns 0. */
+int bcc_set_spend_round(size_t items);
+
 /* The layer below (the role mi_schnorr_verify_tuples has for signatures): n rows of the tweaked
  * key q, the parity byte, the internal key p and the tweak t (32-byte big-endian strings).
  * verdict[i] = 1 iff secp256k1_xonly_pubkey_parse(internal32_i) succeeds and

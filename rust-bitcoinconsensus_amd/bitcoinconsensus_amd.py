@@ -96,6 +96,10 @@ def lib():
                                                ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int), vp, ctypes.c_int]
         L.mi_xonly_tweak_check_tuples.argtypes = [u8p, u8p, u8p, u8p, u8p, sz, ctypes.c_int]
+        L.bcc_taproot_spend_batch.argtypes = [ctypes.POINTER(TaprootSpend), sz,
+                                              ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+        L.bcc_set_spend_round.argtypes = [sz]
         L.bcc_debug_scratch_cap_lanes.argtypes = [sz]
         _bind_consensus(L)
         L.bcc_source_hash.restype = ctypes.c_char_p
@@ -716,6 +720,66 @@ def taproot_commit_batch(items, device=0, tapleaf=False, library=None):
     if tapleaf:
         return out, [hs.raw[32 * i: 32 * i + 32] for i in range(n)]
     return out
+
+
+# script_error.h numbers taproot_spend_batch reports beside the ones above
+SCRIPT_ERR_EVAL_FALSE = 2
+SCRIPT_ERR_PUSH_SIZE = 5
+SCRIPT_ERR_STACK_SIZE = 7
+SCRIPT_ERR_BAD_OPCODE = 15
+SCRIPT_ERR_PUBKEYTYPE = 28
+SCRIPT_ERR_CLEANSTACK = 29
+SCRIPT_ERR_WITNESS_PROGRAM_WITNESS_EMPTY = 38
+SCRIPT_ERR_WITNESS_MALLEATED = 40
+SCRIPT_ERR_TAPSCRIPT_VALIDATION_WEIGHT = 48
+SCRIPT_ERR_TAPSCRIPT_CHECKMULTISIG = 49
+SCRIPT_ERR_TAPSCRIPT_MINIMALIF = 50
+TAPROOT_SPEND_FLAGS = 0xE15 | 1 << 17  # the reference flags taproot_spend_batch stands for
+
+
+class TaprootSpend(ctypes.Structure):
+    """include/bcc_amd.h bcc_taproot_spend."""
+    _fields_ = [("tx", ctypes.c_char_p), ("tx_len", ctypes.c_uint),
+                ("spent_outputs", ctypes.c_char_p), ("spent_outputs_len", ctypes.c_uint),
+                ("n_in", ctypes.c_uint)]
+
+
+def taproot_spend_batch(items, device=0, library=None):
+    """VerifyScript for each input that spends a native v1 witness program, tapscript included
+    (depend/bitcoin/src/script/interpreter.cpp:1937-2056 with VerifyWitnessProgram's v1 branch,
+    :1889-1927; include/bcc_amd.h bcc_taproot_spend_batch).  An item is a dict with keys tx, spent
+    (serialized std::vector<CTxOut>, one per input) and nin.  Returns [(ret, serror)]: (1, 0), or
+    0 with the script_error.h number, or (-1, 1) for an input this entry does not take.  Adjacent
+    items of one tx should pass the same tx / spent bytes objects: they then share the per-tx work.
+    `library`: another build of the same C ABI (tests: the host code over the oracle stub)."""
+    n = len(items)
+    arr = (TaprootSpend * max(n, 1))()
+    keep = []
+    for i, c in enumerate(items):
+        tx, spent = bytes(c["tx"]), bytes(c["spent"])
+        if i and items[i - 1]["tx"] is c["tx"]:
+            tx = keep[-1][0]
+        if i and items[i - 1]["spent"] is c["spent"]:
+            spent = keep[-1][1]
+        keep.append((tx, spent))
+        arr[i] = TaprootSpend(tx, len(tx), spent, len(spent), c["nin"])
+    ret = (ctypes.c_int * max(n, 1))()
+    err = (ctypes.c_int * max(n, 1))()
+    L = library if library is not None else lib()
+    L.bcc_taproot_spend_batch.argtypes = [ctypes.POINTER(TaprootSpend), ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    rc = L.bcc_taproot_spend_batch(arr, n, ret, err, device)
+    if rc != 0:
+        raise RuntimeError(f"bcc_taproot_spend_batch failed: {rc}")
+    return [(ret[i], err[i]) for i in range(n)]
+
+
+def set_spend_round(items, library=None):
+    """bcc_set_spend_round: items per device round of taproot_spend_batch (0: the default)."""
+    L = library if library is not None else lib()
+    L.bcc_set_spend_round.argtypes = [ctypes.c_size_t]
+    L.bcc_set_spend_round(items)
 
 
 def xonly_tweak_check_tuples(tweaked32, parity, internal32, tweak32, device=0):

@@ -30,6 +30,7 @@ enum Op : uint8_t {
     OP_HASH256 = 0xaa, OP_CODESEPARATOR = 0xab, OP_CHECKSIG = 0xac, OP_CHECKSIGVERIFY = 0xad,
     OP_CHECKMULTISIG = 0xae, OP_CHECKMULTISIGVERIFY = 0xaf, OP_NOP1 = 0xb0,
     OP_CHECKLOCKTIMEVERIFY = 0xb1, OP_CHECKSEQUENCEVERIFY = 0xb2, OP_NOP4 = 0xb3, OP_NOP10 = 0xb9,
+    OP_CHECKSIGADD = 0xba,
 };
 
 constexpr size_t MAX_SCRIPT_ELEMENT_SIZE = 520;
@@ -42,6 +43,7 @@ constexpr uint32_t SEQUENCE_FINAL = 0xffffffffu;
 constexpr uint32_t SEQUENCE_LOCKTIME_DISABLE_FLAG = 1u << 31;
 constexpr uint32_t SEQUENCE_LOCKTIME_TYPE_FLAG = 1u << 22;
 constexpr uint32_t SEQUENCE_LOCKTIME_MASK = 0x0000ffffu;
+constexpr int64_t VALIDATION_WEIGHT_PER_SIGOP_PASSED = 50;
 
 struct ScriptNumError : std::runtime_error {
     ScriptNumError() : std::runtime_error("scriptnum") {}
@@ -77,17 +79,7 @@ int num_getint(int64_t v) {
     return (int)v;
 }
 
-bool cast_to_bool(const uint8_t* v, size_t n) {
-    for (size_t i = 0; i < n; i++) {
-        if (v[i] != 0) {
-            if (i == n - 1 && v[i] == 0x80) return false;  // negative zero
-            return true;
-        }
-    }
-    return false;
-}
-
-bool cast_to_bool(const Bytes& v) { return cast_to_bool(v.data(), v.size()); }
+bool cast_to_bool(const Bytes& v) { return host::cast_to_bool(v.data(), v.size()); }
 
 bool fail(ScriptErr* e, ScriptErr code) {
     if (e) *e = code;
@@ -186,19 +178,41 @@ void popstack(std::vector<Bytes>& st) {
     st.pop_back();
 }
 
+// EvalChecksigTapscript (interpreter.cpp:371-429).  false: the script fails with *serror.
+bool eval_checksig_tapscript(const Bytes& sig, const Bytes& pub, TapscriptData& ex,
+                             uint32_t codesep_pos, SigChecker& checker, ScriptErr* serror,
+                             bool& success) {
+    success = !sig.empty();
+    if (success) {  // a passing signature check is paid for before anything is looked at
+        ex.validation_weight_left -= VALIDATION_WEIGHT_PER_SIGOP_PASSED;
+        if (ex.validation_weight_left < 0) return fail(serror, SERR_TAPSCRIPT_VALIDATION_WEIGHT);
+    }
+    if (pub.size() == 0) return fail(serror, SERR_PUBKEYTYPE);
+    if (pub.size() == 32) {
+        if (success && !checker.check_schnorr(sig, pub.data(), codesep_pos))
+            return fail(serror, checker.schnorr_error());
+    }
+    // any other key size is an unknown key type: the check passes (no DISCOURAGE flag here)
+    return true;
+}
+
+// `tap` is set exactly for SIGVERSION_TAPSCRIPT.
 bool eval_script(std::vector<Bytes>& stack, const uint8_t* script, size_t script_len,
-                 unsigned flags, SigChecker& checker, SigVersion sigversion, ScriptErr* serror) {
+                 unsigned flags, SigChecker& checker, SigVersion sigversion, ScriptErr* serror,
+                 TapscriptData* tap = nullptr) {
     static const Bytes vch_false;
     static const Bytes vch_true(1, 1);
     if (serror) *serror = SERR_UNKNOWN;
-    if (script_len > MAX_SCRIPT_SIZE) return fail(serror, SERR_SCRIPT_SIZE);
+    const bool tapscript = sigversion == SIGVERSION_TAPSCRIPT;
+    if (!tapscript && script_len > MAX_SCRIPT_SIZE) return fail(serror, SERR_SCRIPT_SIZE);
+    uint32_t opcode_pos = 0, codesep_pos = 0xFFFFFFFFu;  // BIP342: counted in opcodes
     size_t pc = 0, pbegincodehash = 0;
     const size_t pend = script_len;
     CondStack vf_exec;
     std::vector<Bytes> altstack;
     int op_count = 0;
     try {
-        while (pc < pend) {
+        for (; pc < pend; ++opcode_pos) {
             bool f_exec = vf_exec.all_true();
             uint8_t opcode;
             const uint8_t* pdata = nullptr;
@@ -206,7 +220,8 @@ bool eval_script(std::vector<Bytes>& stack, const uint8_t* script, size_t script
             if (!script_get_op(script, script_len, pc, opcode, &pdata, &plen))
                 return fail(serror, SERR_BAD_OPCODE);
             if (plen > MAX_SCRIPT_ELEMENT_SIZE) return fail(serror, SERR_PUSH_SIZE);
-            if (opcode > OP_16 && ++op_count > MAX_OPS_PER_SCRIPT) return fail(serror, SERR_OP_COUNT);
+            if (!tapscript && opcode > OP_16 && ++op_count > MAX_OPS_PER_SCRIPT)
+                return fail(serror, SERR_OP_COUNT);
             switch (opcode) {  // disabled opcodes fail even when not executed (CVE-2010-5137)
                 case OP_CAT: case OP_SUBSTR: case OP_LEFT: case OP_RIGHT: case OP_INVERT:
                 case OP_AND: case OP_OR: case OP_XOR: case OP_2MUL: case OP_2DIV: case OP_MUL:
@@ -252,6 +267,11 @@ bool eval_script(std::vector<Bytes>& stack, const uint8_t* script, size_t script
                         bool value = false;
                         if (f_exec) {
                             if (stack.size() < 1) return fail(serror, SERR_UNBALANCED_CONDITIONAL);
+                            if (tapscript) {  // minimal IF is a consensus rule of BIP342
+                                const Bytes& v = STACKTOP(-1);
+                                if (v.size() > 1 || (v.size() == 1 && v[0] != 1))
+                                    return fail(serror, SERR_TAPSCRIPT_MINIMALIF);
+                            }
                             value = cast_to_bool(STACKTOP(-1));
                             if (opcode == OP_NOTIF) value = !value;
                             popstack(stack);
@@ -474,12 +494,26 @@ bool eval_script(std::vector<Bytes>& stack, const uint8_t* script, size_t script
                     }
                     case OP_CODESEPARATOR:
                         pbegincodehash = pc;
+                        codesep_pos = opcode_pos;
                         break;
                     case OP_CHECKSIG:
                     case OP_CHECKSIGVERIFY: {
                         if (stack.size() < 2) return fail(serror, SERR_INVALID_STACK_OPERATION);
                         const Bytes& sig = STACKTOP(-2);
                         const Bytes& pub = STACKTOP(-1);
+                        if (tapscript) {
+                            bool ok = true;
+                            if (!eval_checksig_tapscript(sig, pub, *tap, codesep_pos, checker, serror, ok))
+                                return false;
+                            popstack(stack);
+                            popstack(stack);
+                            stack.push_back(ok ? vch_true : vch_false);
+                            if (opcode == OP_CHECKSIGVERIFY) {
+                                if (ok) popstack(stack);
+                                else return fail(serror, SERR_CHECKSIGVERIFY);
+                            }
+                            break;
+                        }
                         // EvalChecksigPreTapscript (interpreter.cpp:345-369)
                         Bytes code(script + pbegincodehash, script + pend);
                         if (sigversion == SIGVERSION_BASE) {
@@ -499,8 +533,24 @@ bool eval_script(std::vector<Bytes>& stack, const uint8_t* script, size_t script
                         }
                         break;
                     }
+                    case OP_CHECKSIGADD: {  // interpreter.cpp:1103-1127; exists in tapscript only
+                        if (!tapscript) return fail(serror, SERR_BAD_OPCODE);
+                        if (stack.size() < 3) return fail(serror, SERR_INVALID_STACK_OPERATION);
+                        const Bytes& sig = STACKTOP(-3);
+                        const int64_t num = num_decode(STACKTOP(-2));
+                        const Bytes& pub = STACKTOP(-1);
+                        bool ok = true;
+                        if (!eval_checksig_tapscript(sig, pub, *tap, codesep_pos, checker, serror, ok))
+                            return false;
+                        popstack(stack);
+                        popstack(stack);
+                        popstack(stack);
+                        stack.push_back(num_encode(num + (ok ? 1 : 0)));
+                        break;
+                    }
                     case OP_CHECKMULTISIG:
                     case OP_CHECKMULTISIGVERIFY: {
+                        if (tapscript) return fail(serror, SERR_TAPSCRIPT_CHECKMULTISIG);
                         // interpreter.cpp:1129-1239
                         int i = 1;
                         if ((int)stack.size() < i) return fail(serror, SERR_INVALID_STACK_OPERATION);
@@ -700,7 +750,94 @@ bool verify_witness_program(const std::vector<Span>& witness, int version, const
     return true;
 }
 
+// IsOpSuccess (script/script.cpp:335-341)
+bool is_op_success(uint8_t op) {
+    return op == 80 || op == 98 || (op >= 126 && op <= 129) || (op >= 131 && op <= 134) ||
+           (op >= 137 && op <= 138) || (op >= 141 && op <= 142) || (op >= 149 && op <= 153) ||
+           (op >= 187 && op <= 254);
+}
+
 }  // namespace
+
+bool cast_to_bool(const uint8_t* v, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        if (v[i] != 0) {
+            if (i == n - 1 && v[i] == 0x80) return false;  // negative zero
+            return true;
+        }
+    }
+    return false;
+}
+
+bool execute_tapscript(std::vector<Bytes> stack, const Span& script, TapscriptData& execdata,
+                       SigChecker& checker, ScriptErr* serror) {
+    // OP_SUCCESSx overrides everything after it, the element size limits included; an opcode that
+    // does not decode before one is found fails the script
+    for (size_t pc = 0; pc < script.n;) {
+        uint8_t op;
+        if (!script_get_op(script.p, script.n, pc, op, nullptr, nullptr))
+            return fail(serror, SERR_BAD_OPCODE);
+        if (is_op_success(op)) {
+            if (serror) *serror = SERR_OK;
+            return true;
+        }
+    }
+    if (stack.size() > MAX_STACK_SIZE) return fail(serror, SERR_STACK_SIZE);
+    for (const auto& e : stack)
+        if (e.size() > MAX_SCRIPT_ELEMENT_SIZE) return fail(serror, SERR_PUSH_SIZE);
+    if (!eval_script(stack, script.p, script.n, FLAGS_VERIFY_ALL, checker, SIGVERSION_TAPSCRIPT,
+                     serror, &execdata))
+        return false;
+    if (stack.size() != 1) return fail(serror, SERR_CLEANSTACK);
+    if (!cast_to_bool(stack.back())) return fail(serror, SERR_EVAL_FALSE);
+    return true;
+}
+
+int script_err_code(ScriptErr e) {
+    switch (e) {
+        case SERR_OK: return 0;
+        case SERR_UNKNOWN: return 1;
+        case SERR_EVAL_FALSE: return 2;
+        case SERR_OP_RETURN: return 3;
+        case SERR_SCRIPT_SIZE: return 4;
+        case SERR_PUSH_SIZE: return 5;
+        case SERR_OP_COUNT: return 6;
+        case SERR_STACK_SIZE: return 7;
+        case SERR_SIG_COUNT: return 8;
+        case SERR_PUBKEY_COUNT: return 9;
+        case SERR_VERIFY: return 10;
+        case SERR_EQUALVERIFY: return 11;
+        case SERR_CHECKMULTISIGVERIFY: return 12;
+        case SERR_CHECKSIGVERIFY: return 13;
+        case SERR_NUMEQUALVERIFY: return 14;
+        case SERR_BAD_OPCODE: return 15;
+        case SERR_DISABLED_OPCODE: return 16;
+        case SERR_INVALID_STACK_OPERATION: return 17;
+        case SERR_INVALID_ALTSTACK_OPERATION: return 18;
+        case SERR_UNBALANCED_CONDITIONAL: return 19;
+        case SERR_NEGATIVE_LOCKTIME: return 20;
+        case SERR_UNSATISFIED_LOCKTIME: return 21;
+        case SERR_SIG_DER: return 23;
+        case SERR_SIG_PUSHONLY: return 25;
+        case SERR_SIG_NULLDUMMY: return 27;
+        case SERR_PUBKEYTYPE: return 28;
+        case SERR_CLEANSTACK: return 29;
+        case SERR_WITNESS_PROGRAM_WRONG_LENGTH: return 37;
+        case SERR_WITNESS_PROGRAM_WITNESS_EMPTY: return 38;
+        case SERR_WITNESS_PROGRAM_MISMATCH: return 39;
+        case SERR_WITNESS_MALLEATED: return 40;
+        case SERR_WITNESS_MALLEATED_P2SH: return 41;
+        case SERR_WITNESS_UNEXPECTED: return 42;
+        case SERR_SCHNORR_SIG_SIZE: return 44;
+        case SERR_SCHNORR_SIG_HASHTYPE: return 45;
+        case SERR_SCHNORR_SIG: return 46;
+        case SERR_TAPROOT_WRONG_CONTROL_SIZE: return 47;
+        case SERR_TAPSCRIPT_VALIDATION_WEIGHT: return 48;
+        case SERR_TAPSCRIPT_CHECKMULTISIG: return 49;
+        case SERR_TAPSCRIPT_MINIMALIF: return 50;
+    }
+    return 1;
+}
 
 bool script_get_op(const uint8_t* s, size_t n, size_t& pc, uint8_t& op, const uint8_t** data,
                    size_t* datalen) {

@@ -2,14 +2,16 @@
 // interpreter on the CPU").  Restates the consensus behaviour of
 //   EvalScript            script/interpreter.cpp:431-1259
 //   VerifyScript          script/interpreter.cpp:1937-2056
-//   VerifyWitnessProgram  script/interpreter.cpp:1855-1935 (witness v0; v1+ pass unchecked
-//                         because SCRIPT_VERIFY_TAPROOT is not a libconsensus flag)
-//   ExecuteWitnessScript  script/interpreter.cpp:1794-1832
+//   VerifyWitnessProgram  script/interpreter.cpp:1855-1935 (witness v0 here; verify_script lets
+//                         v1+ pass unchecked because SCRIPT_VERIFY_TAPROOT is not a libconsensus
+//                         flag; the v1 branch, :1889-1927, is host/taproot_spend.cpp)
+//   ExecuteWitnessScript  script/interpreter.cpp:1794-1832 (execute_tapscript: the TAPSCRIPT side)
+//   EvalChecksigTapscript script/interpreter.cpp:371-429
 //   CScriptNum            script/script.h:218-391
 // for the libconsensus flag set (bitcoinconsensus.h:178-190: P2SH, DERSIG, NULLDUMMY, CLTV,
 // CSV, WITNESS).  Every ECDSA check goes through SigChecker::check_ecdsa — the deferral seam
 // (BaseSignatureChecker::CheckECDSASignature, interpreter.h:227) where the batch engine records
-// tuples for the GPU instead of verifying them.
+// tuples for the GPU instead of verifying them; every BIP342 check through check_schnorr.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -23,7 +25,7 @@ namespace host {
 // interpreter byte vectors (stack elements, script codes) on the small-block pool (pool.h)
 typedef std::vector<uint8_t, PoolAlloc<uint8_t>> Bytes;
 
-enum SigVersion { SIGVERSION_BASE = 0, SIGVERSION_WITNESS_V0 = 1 };
+enum SigVersion { SIGVERSION_BASE = 0, SIGVERSION_WITNESS_V0 = 1, SIGVERSION_TAPSCRIPT = 3 };
 
 // libconsensus flag bits (script/interpreter.h:45-141)
 enum : unsigned {
@@ -71,7 +73,19 @@ enum ScriptErr {
     SERR_WITNESS_MALLEATED,
     SERR_WITNESS_MALLEATED_P2SH,
     SERR_WITNESS_UNEXPECTED,
+    // BIP341 / BIP342 (execute_tapscript, host/taproot_spend.cpp)
+    SERR_PUBKEYTYPE,
+    SERR_SCHNORR_SIG_SIZE,
+    SERR_SCHNORR_SIG_HASHTYPE,
+    SERR_SCHNORR_SIG,
+    SERR_TAPROOT_WRONG_CONTROL_SIZE,
+    SERR_TAPSCRIPT_VALIDATION_WEIGHT,
+    SERR_TAPSCRIPT_CHECKMULTISIG,
+    SERR_TAPSCRIPT_MINIMALIF,
 };
+
+// The ScriptError number (script/script_error.h) of a ScriptErr.
+int script_err_code(ScriptErr e);
 
 // The deferral seam.  check_ecdsa receives exactly what BaseSignatureChecker::CheckECDSASignature
 // receives: the full signature push (DER || hashtype), the pubkey push, the scriptCode (after
@@ -99,6 +113,13 @@ public:
     // the check's result.  false (the default): the script hashes now.
     virtual bool defer_key_hash(const uint8_t*, size_t, const uint8_t*) { return false; }
     virtual bool key_hash_taken() { return false; }
+    // BaseSignatureChecker::CheckSchnorrSignature for SigVersion::TAPSCRIPT: a non-empty signature
+    // met by a 32-byte key, with execdata's OP_CODESEPARATOR position.  false fails the script with
+    // schnorr_error().  A batching checker answers true and records the check: in BIP342 a
+    // non-empty signature either verifies or fails the whole script, so the run never depends on
+    // the verdict.
+    virtual bool check_schnorr(const Bytes&, const uint8_t*, uint32_t) { return false; }
+    virtual ScriptErr schnorr_error() const { return SERR_SCHNORR_SIG; }
     virtual bool check_locktime(int64_t n) = 0;
     virtual bool check_sequence(int64_t n) = 0;
 };
@@ -109,6 +130,21 @@ bool tx_check_sequence(const Tx& tx, unsigned nin, int64_t n);
 
 bool verify_script(const Span& script_sig, const Span& spk, const std::vector<Span>& witness,
                    unsigned flags, SigChecker& checker, ScriptErr* err);
+
+// ScriptExecutionData as far as the interpreter itself uses it (interpreter.h:199-220): the
+// tapleaf hash and the annex matter only to the signature hash, which the checker owns.
+struct TapscriptData {
+    int64_t validation_weight_left = 0;  // serialized witness stack size + 50 (interpreter.cpp:1918)
+};
+
+// ExecuteWitnessScript for SigVersion::TAPSCRIPT (interpreter.cpp:1794-1832): the OP_SUCCESSx
+// pre-scan, the initial stack limits, EvalScript, the clean-stack and truth rules.  `stack` is the
+// witness stack without annex, control block and script.
+bool execute_tapscript(std::vector<Bytes> stack, const Span& script, TapscriptData& execdata,
+                       SigChecker& checker, ScriptErr* err);
+
+// CastToBool (interpreter.cpp:35-49)
+bool cast_to_bool(const uint8_t* v, size_t n);
 
 // helpers shared with the sighash / batch code
 bool script_get_op(const uint8_t* s, size_t n, size_t& pc, uint8_t& op, const uint8_t** data,

@@ -22,6 +22,7 @@
 #include "devices.h"
 #include "engine.h"
 #include "hashes.h"
+#include "taproot_jobs.h"
 #include "team.h"
 #include "tuples.h"
 #include "tx.h"
@@ -52,74 +53,6 @@ struct RoundOut {
 };
 thread_local RoundOut tl_round_out[TAPROOT_SLOTS];
 
-// The parsed tx (and spent outputs) an adjacent run of items shares, and its TtxRec in the
-// current part.
-struct TxState {
-    const uint8_t* tx = nullptr;
-    unsigned tx_len = 0;
-    const uint8_t* spent = nullptr;
-    unsigned spent_len = 0;
-    bool ok = false;
-    Tx t;
-    std::vector<TxOut> outs;
-    int32_t ttx = -1;  // TtxRec index in the current part (-1: not added yet)
-};
-
-// The tx (without marker, flag and witnesses: the SigMsg kernels never read them) and the outputs
-// it spends, once per part.
-uint32_t tx_record(TxState& s, TaprootTxJobs& D) {
-    if (s.ttx >= 0) return (uint32_t)s.ttx;
-    TtxRec r{};
-    r.tx_off = (uint32_t)D.txraw.size();
-    const uint8_t* raw = s.tx;
-    const size_t len = s.tx_len;
-    if (s.t.has_witness() && !s.t.vout.empty() && len > 10) {  // BIP144: inputs start at byte 6
-        const Span& last = s.t.vout.back().ser;
-        const size_t mid = (size_t)(last.p + last.n - (raw + 6));
-        D.put_raw(raw, 4);
-        D.put_raw(raw + 6, mid);
-        D.put_raw(raw + len - 4, 4);
-        r.tx_len = (uint32_t)(8 + mid);
-    } else {
-        D.put_raw(raw, len);
-        r.tx_len = (uint32_t)len;
-    }
-    D.align4();
-    r.sp_off = (uint32_t)D.txraw.size();
-    r.sp_len = s.spent_len;
-    D.put_raw(s.spent, s.spent_len);
-    D.align4();
-    r.in_base = D.in_entries;
-    r.n_in = (uint32_t)s.t.vin.size();
-    D.in_entries += r.n_in;
-    D.ttx.push_back(r);
-    s.ttx = (int32_t)D.ttx.size() - 1;
-    return (uint32_t)s.ttx;
-}
-
-bool load_tx(TxState& s, const bcc_taproot_check& it) {
-    if (s.tx == it.tx && s.tx_len == it.tx_len && s.spent == it.spent_outputs &&
-        s.spent_len == it.spent_outputs_len && s.tx)
-        return s.ok;
-    s.tx = it.tx;
-    s.tx_len = it.tx_len;
-    s.spent = it.spent_outputs;
-    s.spent_len = it.spent_outputs_len;
-    s.ttx = -1;
-    s.ok = it.tx && it.spent_outputs && parse_tx(it.tx, it.tx_len, s.t) &&
-           s.t.ser_size == it.tx_len && parse_txouts(it.spent_outputs, it.spent_outputs_len, s.outs) &&
-           s.outs.size() == s.t.vin.size();
-    if (s.ok) {
-        // m_bip341_taproot_ready (interpreter.cpp:1436-1452); SignatureHashSchnorr asserts it
-        bool ready = false;
-        for (size_t i = 0; i < s.t.vin.size() && !ready; i++)
-            ready = !s.t.vin[i].witness.empty() && s.outs[i].script.size() == 34 &&
-                    s.outs[i].script.p[0] == 0x51;
-        s.ok = ready;
-    }
-    return s.ok;
-}
-
 // Items [lo, hi): resolve on the host what needs no hashing, build the SigMsg jobs for the rest.
 void build_part(const bcc_taproot_check* items, size_t lo, size_t hi, int* ret, int* serr,
                 Part& P) {
@@ -139,67 +72,21 @@ void build_part(const bcc_taproot_check* items, size_t lo, size_t hi, int* ret, 
         const bcc_taproot_check& it = items[i];
         ret[i] = 0;
         serr[i] = 0;
-        if (!load_tx(s, it) || it.n_in >= s.t.vin.size() || !it.pubkey32 ||
-            (it.sig_len && !it.sig) ||
+        if (!load_tx(s, it.tx, it.tx_len, it.spent_outputs, it.spent_outputs_len) ||
+            it.n_in >= s.t.vin.size() || !it.pubkey32 || (it.sig_len && !it.sig) ||
             (it.sigversion != BCC_SIGVERSION_TAPROOT && it.sigversion != BCC_SIGVERSION_TAPSCRIPT) ||
             (it.sigversion == BCC_SIGVERSION_TAPSCRIPT && !it.tapleaf_hash32)) {
             ret[i] = -1;
             serr[i] = SCRIPT_ERR_UNKNOWN_ERROR;
             continue;
         }
-        // CheckSchnorrSignature (interpreter.cpp:1688-1700)
-        if (it.sig_len != 64 && it.sig_len != 65) {
-            serr[i] = BCC_SCRIPT_ERR_SCHNORR_SIG_SIZE;
+        if (int e = taproot_add_check(s, J, it.n_in, it.sig, it.sig_len, it.pubkey32,
+                                      it.sigversion == BCC_SIGVERSION_TAPSCRIPT, it.annex,
+                                      it.annex_len, it.tapleaf_hash32, it.codeseparator_pos, scratch)) {
+            serr[i] = e;
             continue;
         }
-        uint8_t hash_type = 0;  // SIGHASH_DEFAULT
-        if (it.sig_len == 65) {
-            hash_type = it.sig[64];
-            if (hash_type == 0) {
-                serr[i] = BCC_SCRIPT_ERR_SCHNORR_SIG_HASHTYPE;
-                continue;
-            }
-        }
-        // SignatureHashSchnorr's early returns (:1523, :1557)
-        const int output_type = hash_type == 0 ? 1 : (hash_type & 3);
-        if (!(hash_type <= 0x03 || (hash_type >= 0x81 && hash_type <= 0x83)) ||
-            (output_type == 3 && it.n_in >= s.t.vout.size())) {
-            serr[i] = BCC_SCRIPT_ERR_SCHNORR_SIG_HASHTYPE;
-            continue;
-        }
-        const bool annex = it.annex != nullptr;
-        const bool tapscript = it.sigversion == BCC_SIGVERSION_TAPSCRIPT;
-        {  // the SigMsg is assembled on the device (taproot_msg_kernel) from the tx bytes
-            TaprootTxJobs& D = J.dev;
-            TapJob tj{};
-            tj.ttx = tx_record(s, D);
-            tj.nin = it.n_in;
-            tj.hash_type = hash_type;
-            tj.spend_type = ((tapscript ? 1u : 0u) << 1) + (annex ? 1u : 0u);
-            tj.ext_off = (uint32_t)D.ext.size();
-            if (annex) {  // sha_annex = SHA256(compactsize(len) || annex)
-                scratch.clear();
-                put_compact_size(scratch, it.annex_len);
-                scratch.insert(scratch.end(), it.annex, it.annex + it.annex_len);
-                D.ext.resize(D.ext.size() + 32);
-                sha256(scratch.data(), scratch.size(), &D.ext[D.ext.size() - 32]);
-            }
-            if (output_type == 3) {  // sha_single_output
-                const TxOut& o = s.t.vout[it.n_in];
-                D.ext.resize(D.ext.size() + 32);
-                sha256(o.ser.p, o.ser.n, &D.ext[D.ext.size() - 32]);
-            }
-            if (tapscript) {
-                D.ext.insert(D.ext.end(), it.tapleaf_hash32, it.tapleaf_hash32 + 32);
-                tj.flags = 1;
-                tj.codesep = it.codeseparator_pos;
-            }
-            tj.row = (uint32_t)J.rows();
-            D.jobs.push_back(tj);
-            J.sig64.insert(J.sig64.end(), it.sig, it.sig + 64);
-            J.pk32.insert(J.pk32.end(), it.pubkey32, it.pubkey32 + 32);
-            P.item_of_row.push_back((uint32_t)i);
-        }
+        P.item_of_row.push_back((uint32_t)i);
     }
 }
 

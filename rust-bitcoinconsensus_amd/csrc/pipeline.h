@@ -429,6 +429,22 @@ constexpr int TAPROOT_SLOTS = 3;
 int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* parts, size_t P);
 int gpu_taproot_end(int device, int slot, uint8_t* verdict, uint8_t* msg32_out);
 
+// begin / end with a guest stage in the same round (bcc_taproot_spend_batch's commitments,
+// taproot_commit.hip): up_bytes more of the pinned image, written by fill() and uploaded in the
+// round's one copy, and dev_bytes of device-only memory behind them.  launch() queues the guest's
+// kernels on the round's stream behind the upload and before the SigMsg kernels, so it may write
+// the ext blob (d_ext) they read.  The first out_bytes of the device-only block travel back with
+// the verdicts (gpu_taproot_end_extra's extra_out).  A round may have no rows at all.
+struct TaprootExtra {
+    size_t up_bytes = 0, dev_bytes = 0, out_bytes = 0;
+    std::function<void(uint8_t* h_up)> fill;
+    std::function<int(void* stream, uint8_t* d_up, uint8_t* d_dev, uint8_t* d_ext)> launch;
+};
+int gpu_taproot_begin_extra(int device, int slot, const TaprootJobs* const* parts, size_t P,
+                            const TaprootExtra* extra);
+int gpu_taproot_end_extra(int device, int slot, uint8_t* verdict, uint8_t* msg32_out,
+                          uint8_t* extra_out);
+
 // Device scratch of the signature kernels: s^-1 rows (ECDSA) and, for one chunk of lanes, the
 // Q tables + ladder states.  Every synchronous entry point owns one per (thread, device), so
 // concurrent callers never share scratch (the reference ABI is reentrant).  Launches

@@ -2165,6 +2165,8 @@ struct TaprootCtx {
     int dev = -1;
     hipStream_t stream = nullptr;
     size_t n = 0, off_verdict = 0, off_msg = 0;  // the round launched by gpu_taproot_begin
+    size_t xout = 0;  // its guest stage's bytes behind the verdicts in vpin (16-aligned start)
+    bool live = false;  // a round (rows or a guest stage) was queued and not yet ended
     SigScratch sc;
     void* arena = nullptr;
     size_t cap = 0;
@@ -2214,6 +2216,15 @@ int gpu_taproot_verify_parts(int device, const TaprootJobs* const* Jp, size_t P,
 }
 
 int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t P) {
+    return gpu_taproot_begin_extra(device, slot, Jp, P, nullptr);
+}
+
+int gpu_taproot_end(int device, int slot, uint8_t* verdict, uint8_t* msg32_out) {
+    return gpu_taproot_end_extra(device, slot, verdict, msg32_out, nullptr);
+}
+
+int gpu_taproot_begin_extra(int device, int slot, const TaprootJobs* const* Jp, size_t P,
+                            const TaprootExtra* X) {
     std::vector<size_t> row0(P + 1, 0), aux0(P + 1, 0), msg0(P + 1, 0), auxi0(P + 1, 0),
         msgi0(P + 1, 0), pat0(P + 1, 0), raw0(P + 1, 0), ttx0(P + 1, 0), tj0(P + 1, 0),
         ext0(P + 1, 0), in0(P + 1, 0);
@@ -2233,8 +2244,11 @@ int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t
     }
     const size_t n = row0[P];
     if (device < 0 || device >= 64 || slot < 0 || slot >= TAPROOT_SLOTS) return (int)hipErrorInvalidDevice;
-    if (n == 0) {
-        if (tl_taproot_ctxs[device][slot]) tl_taproot_ctxs[device][slot]->n = 0;
+    if (n == 0 && !X) {
+        if (tl_taproot_ctxs[device][slot]) {
+            tl_taproot_ctxs[device][slot]->n = 0;
+            tl_taproot_ctxs[device][slot]->live = false;
+        }
         return 0;
     }
     if (aux0[P] >= ((size_t)1 << 32) || msg0[P] >= ((size_t)1 << 32) || raw0[P] >= ((size_t)1 << 32) ||
@@ -2252,6 +2266,8 @@ int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t
     }
     TaprootCtx& c = *slot_ctx;
     c.n = 0;
+    c.xout = 0;
+    c.live = false;
     // this slot's previous round must be done with the arena and the pinned image
     if (hipStreamSynchronize(c.stream) != hipSuccess) {
         slot_ctx.reset();
@@ -2260,10 +2276,10 @@ int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t
     BCC_HIP_TRY(hipSetDevice(device));
     const size_t naux = auxi0[P], nmsg = msgi0[P], npat = pat0[P], nttx = ttx0[P], ntj = tj0[P];
     // layout: sig64 | pk32 | msg32 | verdict | aux | msg | aux_off | aux_nblk | msg_off |
-    //         msg_nblk | msg_row | patches | txraw | TtxRec | TapJob | ext || aux digests |
-    //         input table | tx digests (the last three not uploaded)
+    //         msg_nblk | msg_row | patches | txraw | TtxRec | TapJob | ext | guest upload ||
+    //         aux digests | input table | tx digests | guest device block (the last four not uploaded)
     enum { SIG, PK, MSG, VER, AUX, MSGB, AUX_OFF, AUX_NBLK, MSG_OFF, MSG_NBLK, MSG_ROW, PATCH, TXRAW,
-           TTX, TJOB, EXT, UPLOADED, AUXD = UPLOADED, INTAB, TTXD, NB };
+           TTX, TJOB, EXT, XUP, UPLOADED, AUXD = UPLOADED, INTAB, TTXD, XDEV, NB };
     size_t sizes[NB] = {};
     sizes[SIG] = 64 * n; sizes[PK] = 32 * n; sizes[MSG] = 32 * n; sizes[VER] = n;
     sizes[AUX] = aux0[P]; sizes[MSGB] = msg0[P]; sizes[AUX_OFF] = sizes[AUX_NBLK] = 4 * naux;
@@ -2271,6 +2287,11 @@ int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t
     sizes[PATCH] = sizeof(PatchRec) * npat; sizes[TXRAW] = raw0[P] + 64;
     sizes[TTX] = sizeof(TtxRec) * nttx; sizes[TJOB] = sizeof(TapJob) * ntj; sizes[EXT] = ext0[P];
     sizes[AUXD] = 32 * naux; sizes[INTAB] = 16 * in0[P]; sizes[TTXD] = 160 * nttx;
+    const size_t xout = X ? (X->out_bytes + 15) & ~(size_t)15 : 0;
+    if (X) {
+        sizes[XUP] = X->up_bytes;
+        sizes[XDEV] = std::max(X->dev_bytes, xout);
+    }
     size_t off[NB], total = 0;
     for (int i = 0; i < NB; i++) {
         off[i] = total;
@@ -2339,11 +2360,18 @@ int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t
         }
     };
     host::run_team((unsigned)P, [&](unsigned q) { fill(q); });
+    if (X && X->fill) X->fill(h + off[XUP]);
     uint8_t* a = (uint8_t*)c.arena;
     hipStream_t st = c.stream;
     ShaMid mid;
     tapsighash_midstate(mid.s);
     BCC_HIP_TRY(hipMemcpyAsync(a, h, upload, hipMemcpyHostToDevice, st));
+    if (X && X->launch) {  // the guest stage: behind the upload, ahead of the ext blob's readers
+        if (int e = X->launch((void*)st, a + off[XUP], a + off[XDEV], a + off[EXT])) {
+            slot_ctx.reset();
+            return e;
+        }
+    }
     if (nttx) {  // KT_tx, then KT_msg: the SigMsgs from the tx bytes
         hipLaunchKernelGGL(taproot_tx_kernel, dim3((unsigned)((5 * nttx + XS_WG - 1) / XS_WG)),
                            dim3(XS_WG), 0, st, a + off[TXRAW], (const TtxRec*)(a + off[TTX]),
@@ -2377,46 +2405,62 @@ int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t
                            (const uint32_t*)(a + off[MSG_ROW]), mid);
         BCC_HIP_TRY(hipGetLastError());
     }
-    if (int e = schnorr_launch(c.sc, a + off[0], a + off[2], a + off[1], a + off[3], n, st)) {
-        slot_ctx.reset();
-        return e;
+    if (n) {
+        if (int e = schnorr_launch(c.sc, a + off[0], a + off[2], a + off[1], a + off[3], n, st)) {
+            slot_ctx.reset();
+            return e;
+        }
     }
-    if (n > c.vcap) {
+    const size_t n16 = (n + 15) & ~(size_t)15;  // the guest's bytes follow the verdicts, 16-aligned
+    if (n16 + xout > c.vcap) {
         if (c.vpin) BCC_HIP_TRY(hipHostFree(c.vpin));
         c.vpin = nullptr;
         c.vcap = 0;
-        BCC_HIP_TRY(hipHostMalloc((void**)&c.vpin, (n + 15) & ~(size_t)15, hipHostMallocDefault));
+        BCC_HIP_TRY(hipHostMalloc((void**)&c.vpin, n16 + xout, hipHostMallocDefault));
         BCC_HIP_TRY(hipHostGetDevicePointer((void**)&c.vpin_dev, c.vpin, 0));
-        c.vcap = n;
+        c.vcap = n16 + xout;
     }
-    hipLaunchKernelGGL(bytes_to_host_kernel, dim3((unsigned)(((n + 15) / 16 + 255) / 256)), dim3(256), 0, st,
-                       (const uint4*)(a + off[3]), (uint4*)c.vpin_dev, (uint32_t)((n + 15) / 16));
-    BCC_HIP_TRY(hipGetLastError());
+    if (n) {
+        hipLaunchKernelGGL(bytes_to_host_kernel, dim3((unsigned)((n16 / 16 + 255) / 256)), dim3(256), 0, st,
+                           (const uint4*)(a + off[3]), (uint4*)c.vpin_dev, (uint32_t)(n16 / 16));
+        BCC_HIP_TRY(hipGetLastError());
+    }
+    if (xout) {
+        hipLaunchKernelGGL(bytes_to_host_kernel, dim3((unsigned)((xout / 16 + 255) / 256)), dim3(256), 0, st,
+                           (const uint4*)(a + off[XDEV]), (uint4*)(c.vpin_dev + n16), (uint32_t)(xout / 16));
+        BCC_HIP_TRY(hipGetLastError());
+    }
+    c.xout = X ? X->out_bytes : 0;
+    c.live = true;
     c.n = n;
     c.off_verdict = off[3];
     c.off_msg = off[2];
     return 0;
 }
 
-int gpu_taproot_end(int device, int slot, uint8_t* verdict, uint8_t* msg32_out) {
+int gpu_taproot_end_extra(int device, int slot, uint8_t* verdict, uint8_t* msg32_out,
+                          uint8_t* extra_out) {
     if (device < 0 || device >= 64 || slot < 0 || slot >= TAPROOT_SLOTS) return (int)hipErrorInvalidDevice;
     auto& slot_ctx = tl_taproot_ctxs[device][slot];
-    if (!slot_ctx || slot_ctx->n == 0) return 0;
+    if (!slot_ctx || !slot_ctx->live) return 0;
     TaprootCtx& c = *slot_ctx;
     BCC_HIP_TRY(hipSetDevice(device));
     const uint8_t* a = (const uint8_t*)c.arena;
-    const size_t n = c.n;
+    const size_t n = c.n, xout = c.xout;
     c.n = 0;
+    c.xout = 0;
+    c.live = false;
     int rc = 0;
     // the verdicts' copy was queued by gpu_taproot_begin
-    if ((msg32_out && (rc = (int)hipMemcpyAsync(msg32_out, a + c.off_msg, 32 * n,
+    if ((msg32_out && n && (rc = (int)hipMemcpyAsync(msg32_out, a + c.off_msg, 32 * n,
                                                 hipMemcpyDeviceToHost, c.stream))) ||
         (rc = (int)hipStreamSynchronize(c.stream))) {
         fprintf(stderr, "[bcc] gpu_taproot_verify failed: %d\n", rc);
         slot_ctx.reset();  // a retry starts from a fresh stream / arena / scratch
         return rc;
     }
-    memcpy(verdict, c.vpin, n);
+    if (n) memcpy(verdict, c.vpin, n);
+    if (extra_out && xout) memcpy(extra_out, c.vpin + ((n + 15) & ~(size_t)15), xout);
     return 0;
 }
 

@@ -15,6 +15,10 @@
 //                                lanes per thread (one inversion per group, as twist_fin_kernel),
 //                                then x(R) == q and the parity of y(R).  A decided lane multiplies
 //                                nothing into its group's product.
+//   K_leaf   leaf_copy_kernel    bcc_taproot_spend_batch only: one lane per queued tapscript
+//                                signature check, K_chash's TapLeaf hash of the check's spend into
+//                                the check's slot of the SigMsg ext blob (HBM to HBM: the hash
+//                                never visits the host).
 // The host half lives here rather than under csrc/host because it launches kernels: csrc/host is
 // also built into the CPU tests' device-less engine.
 #include "gpu_common.h"
@@ -23,6 +27,7 @@
 #include "host/tuples.h"
 #include "pipeline.h"
 #include "taproot_commit.h"
+#include "taproot_spend.h"
 
 #include <functional>
 
@@ -380,6 +385,120 @@ int commit_range(int device, const bcc_taproot_commit* items, size_t n, int* ret
     }
     return 0;
 }
+
+// ---- whole spends (bcc_taproot_spend_batch) ------------------------------------------------
+
+// One lane per queued check: 32 bytes from the leaf-hash row of its spend's commitment lane to
+// its slot in the ext blob, with the widest stores the slot's alignment allows (a slot follows
+// 32-byte entries in a 256-aligned blob, so 16-byte stores in practice; the narrower paths keep
+// the kernel right for any 4- or 1-aligned layout).  Two lanes never share a slot.
+__global__ __launch_bounds__(256) void leaf_copy_kernel(const u32* __restrict__ leaf_row,
+                                                        const LeafCopy* __restrict__ copies,
+                                                        uint8_t* __restrict__ ext, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const LeafCopy c = copies[i];
+    const uint4* src = reinterpret_cast<const uint4*>(leaf_row + 8 * (size_t)c.lane);
+    const uint4 d0 = src[0], d1 = src[1];
+    uint8_t* dst = ext + c.ext_byte;
+    if ((c.ext_byte & 15u) == 0) {
+        uint4* o = reinterpret_cast<uint4*>(dst);
+        o[0] = d0;
+        o[1] = d1;
+    } else if ((c.ext_byte & 3u) == 0) {
+        const u32 w[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+        u32* o = reinterpret_cast<u32*>(dst);
+#pragma unroll
+        for (int k = 0; k < 8; k++) o[k] = w[k];
+    } else {
+        const u32 w[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+        for (int k = 0; k < 32; k++) dst[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
+}
+
+// The fused round: the commitment rows ride in the Taproot round's one upload
+// (gpu_taproot_begin_extra), K_chash / K_tadd / K_tfin and K_leaf run on its stream ahead of the
+// SigMsg kernels, and the commitment verdicts come back with the signature verdicts.
+int spend_begin(int device, int slot, const SpendRound& R) {
+    const size_t P = R.P;
+    std::vector<size_t> c0(P + 1, 0), k0(P + 1, 0), e0(P + 1, 0);
+    std::vector<const TaprootJobs*> pj(P);
+    for (size_t q = 0; q < P; q++) {
+        const SpendPart& S = *R.parts[q];
+        c0[q + 1] = c0[q] + S.commits.size();
+        k0[q + 1] = k0[q] + S.copies.size();
+        e0[q + 1] = e0[q] + S.jobs.dev.ext.size();
+        pj[q] = &S.jobs;
+        for (const LeafCopy& c : S.copies)  // the kernel's only indices: checked before it runs
+            if (c.lane >= S.commits.size() || (size_t)c.ext_byte + 32 > S.jobs.dev.ext.size())
+                return (int)hipErrorInvalidValue;
+    }
+    const size_t n = c0[P], nk = k0[P];
+    if (e0[P] >= ((size_t)1 << 32)) return (int)hipErrorInvalidValue;
+    if (n == 0) return gpu_taproot_begin_extra(device, slot, pj.data(), P, nullptr);
+    // one item array for commit_plan / commit_fill (40 bytes an item)
+    std::vector<bcc_taproot_commit> items(n);
+    for (size_t q = 0; q < P; q++)
+        std::copy(R.parts[q]->commits.begin(), R.parts[q]->commits.end(), items.begin() + c0[q]);
+    std::vector<CommitLane> lanes(n);
+    size_t lb = 0, nd = 0;
+    commit_plan(items.data(), n, lanes.data(), &lb, &nd);
+    if (lb >= ((size_t)1 << 32) || nd >= ((size_t)1 << 32)) return (int)hipErrorInvalidValue;
+    // uploaded: lanes | p | q | parity | nodes | leaf | copies; device only: verdict | leaf hashes |
+    // t | curve scratch
+    const size_t row = align256(32 * n);
+    const size_t o_p = align256(sizeof(CommitLane) * n), o_q = o_p + row, o_par = o_q + row,
+                 o_nodes = o_par + align256(n), o_leaf = o_nodes + align256(32 * nd),
+                 o_cp = o_leaf + align256(64 * lb), up = o_cp + align256(sizeof(LeafCopy) * nk);
+    const size_t stride = std::min(n, CURVE_CHUNK);
+    const size_t d_v = 0, d_lh = align256(n), d_t = d_lh + row, d_s = d_t + row;
+    TaprootExtra X;
+    X.up_bytes = up;
+    X.dev_bytes = d_s + scratch_bytes(stride);
+    X.out_bytes = n;
+    X.fill = [&](uint8_t* h) {
+        memcpy(h, lanes.data(), sizeof(CommitLane) * n);
+        host::pfor(n, 1 << 12, [&](size_t lo, size_t hi) {
+            commit_fill(items.data(), lanes.data(), lo, hi, h + o_p, h + o_q, h + o_par, h + o_nodes,
+                        h + o_leaf);
+        });
+        LeafCopy* cp = reinterpret_cast<LeafCopy*>(h + o_cp);
+        for (size_t q = 0; q < P; q++) {
+            const SpendPart& S = *R.parts[q];
+            for (size_t k = 0; k < S.copies.size(); k++)
+                cp[k0[q] + k] = LeafCopy{S.copies[k].lane + (uint32_t)c0[q],
+                                         S.copies[k].ext_byte + (uint32_t)e0[q]};
+        }
+    };
+    X.launch = [&](void* stream, uint8_t* u, uint8_t* d, uint8_t* d_ext) -> int {
+        hipStream_t st = (hipStream_t)stream;
+        KernelTimer kt;
+        kt.st = st;
+        hipLaunchKernelGGL(commit_hash_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                           (const CommitLane*)u, (const u32*)(u + o_leaf), (const u32*)(u + o_nodes),
+                           (const u32*)(u + o_p), (u32*)(d + d_t), (u32*)(d + d_lh), n, mids());
+        BCC_HIP_TRY(hipGetLastError());
+        if (int e = curve_launch(u + o_p, u + o_q, u + o_par, d + d_t, d + d_v, n, (u32*)(d + d_s),
+                                 stride, st, kt))
+            return e;
+        if (nk) {
+            hipLaunchKernelGGL(leaf_copy_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st,
+                               (const u32*)(d + d_lh), (const LeafCopy*)(u + o_cp), d_ext, (uint32_t)nk);
+            BCC_HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    };
+    return gpu_taproot_begin_extra(device, slot, pj.data(), P, &X);
+}
+
+int spend_end(int device, int slot, uint8_t* commit_verdict, uint8_t* sig_verdict) {
+    return gpu_taproot_end_extra(device, slot, sig_verdict, nullptr, commit_verdict);
+}
+
+const SpendDeviceHook spend_hook{spend_begin, spend_end};
+// library load: the host pass (host/taproot_spend.cpp) finds the device round here
+const bool spend_hook_set = (g_spend_device_hook = &spend_hook, true);
 
 // Contiguous ranges of [0, n) over the configured devices (device = -1) or the one given.
 int over_devices(int device, size_t n, const std::function<int(int, size_t, size_t)>& f) {
