@@ -1,21 +1,33 @@
 // ECDSA verify on gfx950: stages (b) and (c) of the hot path.  One lane = one tuple.
 //
-// Default, square-root-free path (ecdsa_twist.h):
-//   K_inv     batch_sinv_kernel     s^-1 mod n by Montgomery's trick over strided chunks of <= 16
-//                                   tuples (3 mults/tuple + one sliding-window Fermat inversion)
-//   K_tprep   ecdsa_tprep_kernel    key parse without a square root, v = x^3 + 7, Q_w = (x v, v^2),
-//                                   u1 u2, GLV split, co-Z Q_w table
-//   K_tladder twist_ladder_kernel   B = u2 Q_w (Strauss, shared doublings), A = u1 G (fixed-base
-//                                   comb from HBM tables), alpha / beta / K of the x-test
-//   K_tfin    twist_fin_kernel      batched beta^-1, "gamma = -alpha / beta is the key's y",
-//                                   exact fallback for the exceptional lanes
-// BIP340 runs one fused prep + ladder launch (schnorr_tladder_kernel, round 4) and
-// twist_fin_kernel<true>.  (The round-1
-// path -- key decompression by a square root, G tables in LDS -- was retired in round 4.)
-// K_inv needs only the s rows: DeviceBatch::run launches it on a side stream beside the sighash
-// kernels.  Prep and ladder are separate launches so that each gets its own register allocation
-// (ladder: 4 waves per SIMD).  Tuples are processed in chunks of up to 16M lanes so the per-tuple
-// scratch (Q table + ladder state, ~1.4 KB) stays bounded.
+// Every path is square-root-free (ecdsa_twist.h).  The launches, in order:
+//
+// ECDSA, split path (a round that fits one scratch chunk; ecdsa_launch_pre, ecdsa_launch_q /
+// ecdsa_launch_q_mapped, ecdsa_launch_after_pre):
+//   K_inv     batch_sinv_kernel        s^-1 mod n by Montgomery's trick over strided chunks of <= 16
+//                                      tuples (3 mults/tuple + one safegcd inversion per thread)
+//   K_copy    keyq_copy_kernel         only with early twins: their key half and parked B copied
+//   K_keyq    twist_keyq_kernel        key parse without a square root, v = x^3 + 7, Q_w = (x v, v^2),
+//                                      co-Z Q_w table, r / s checks, u2 = r s^-1, GLV split,
+//                                      B = u2 Q_w.  Two launches when the round is not a whole number
+//                                      of residency rounds; twist_keyq2_kernel (two lanes per tuple)
+//                                      for a round of at most one wave per SIMD
+//   K_tladder_g twist_ladder_g_kernel  u1 = m s^-1, A = u1 G (fixed-base comb from HBM tables), the
+//                                      combine, alpha / beta / K of the x-test
+//   K_tfin    twist_fin_kernel<false>  batched beta^-1, "gamma = -alpha / beta is the key's y",
+//                                      exact fallback for the exceptional lanes
+// ECDSA, chunked path (a round above the scratch chunk): K_inv once, then per chunk
+//   K_tprep   ecdsa_tprep_kernel       key parse, Q_w table, u1, u2, GLV split
+//   K_tladder twist_ladder_kernel<false>  B = u2 Q_w (Strauss, shared doublings) and A = u1 G in one
+//                                      launch, alpha / beta / K
+//   K_tfin    twist_fin_kernel<false>
+// BIP340 (schnorr_launch), per chunk:
+//   K_stladder schnorr_tladder_kernel  the prep and the ladder fused (round 4)
+//   K_tfin    twist_fin_kernel<true>
+// K_inv needs only the s rows and K_keyq no message: DeviceBatch::run launches them on a side
+// stream beside the sighash kernels.  Q half and G half are separate launches so that each gets its
+// own register allocation (4 waves per SIMD).  Tuples are processed in chunks of up to 16M lanes so
+// the per-tuple scratch (Q table + ladder state, ~1.4 KB) stays bounded.
 //
 // HBM layout (all device-resident):
 //   tag[n]            u8   pubkey header byte (0 = rejected by the host length filter)
@@ -617,7 +629,7 @@ __global__ __launch_bounds__(TLADDER_WG) __attribute__((amdgpu_waves_per_eu(BCC_
 }
 
 // beta^-1 for every normal lane of a chunk by Montgomery's trick over the strided sub-chunk
-// {t, t+T, ...} (3 mults per lane + one Fermat inversion per thread), then the verdicts; the
+// {t, t+T, ...} (3 mults per lane + one safegcd inversion per thread), then the verdicts; the
 // exceptional lanes (adversarial only) run the exact fallback here, divergently.
 template <bool BIP340>
 __device__ __forceinline__ void twist_fin_elem(const u32* w, fe& c) {  // the inverted element
@@ -824,11 +836,7 @@ static int ensure_scratch(SigScratch& sc, int dev, size_t n, bool with_sinv, siz
     return 0;
 }
 
-int ecdsa_launch_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x,
-                     const uint8_t* d_y, const uint8_t* d_s, size_t n, void* stream) {
-    (void)d_tag;
-    (void)d_x;
-    (void)d_y;
+int ecdsa_launch_pre(SigScratch& sc, const uint8_t* d_s, size_t n, void* stream) {
     if (n == 0) return 0;
     int dev = 0, cus = 0;
     const u32* gcomb = nullptr;
@@ -840,26 +848,6 @@ int ecdsa_launch_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x,
     hipLaunchKernelGGL(batch_sinv_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, d_s, (u32*)sc.sinv, n, T);
     BCC_HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The key half runs inside the fused Q launch (twist_keyq_kernel, ecdsa_launch_q): this only
-// marks the round's keys as handled there when the round fits one scratch chunk.
-int ecdsa_launch_key(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x,
-                     const uint8_t* d_y, size_t n, void* stream) {
-    (void)d_tag;
-    (void)d_x;
-    (void)d_y;
-    (void)stream;
-    sc.key_ready = 0;
-    if (n == 0 || n > chunk_lanes()) return 0;
-    int dev = 0, cus = 0;
-    const u32* gcomb = nullptr;
-    size_t C = 0;
-    if (int e = device_tables(&dev, &gcomb, &cus)) return e;
-    if (int e = ensure_scratch(sc, dev, n, true, &C)) return e;
-    if (n > C) return 0;  // chunked: the whole prep runs per chunk after K_inv
-    sc.key_ready = n;
     return 0;
 }
 
@@ -964,13 +952,13 @@ static int launch_keyq(SigScratch& sc, int cus, const uint8_t* d_tag, const uint
 int ecdsa_launch_q(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x, const uint8_t* d_y,
                    const uint8_t* d_r, const uint8_t* d_s, size_t n, void* stream) {
     sc.q_ready = 0;
-    if (n == 0 || sc.key_ready != n || n > chunk_lanes()) return 0;
+    if (n == 0 || n > chunk_lanes()) return 0;
     int dev = 0, cus = 0;
     const u32* gcomb = nullptr;
     size_t C = 0;
     if (int e = device_tables(&dev, &gcomb, &cus)) return e;
     if (int e = ensure_scratch(sc, dev, n, true, &C)) return e;
-    if (n > C) return 0;
+    if (n > C) return 0;  // chunked: the whole prep runs per chunk after K_inv
     u32* qtab = (u32*)sc.chunk;
     u32* state = qtab + C * QTABLE_WORDS;
     if (int e = launch_keyq(sc, cus, d_tag, d_x, d_y, d_r, d_s, n, qtab, state, nullptr, 0,
@@ -987,13 +975,13 @@ int ecdsa_launch_q_mapped(SigScratch& sc, const SigScratch& early, size_t early_
     if (!d_emap || early_n == 0 || !early.chunk)
         return ecdsa_launch_q(sc, d_tag, d_x, d_y, d_r, d_s, n, stream);
     sc.q_ready = 0;
-    if (n == 0 || sc.key_ready != n || n > chunk_lanes()) return 0;
+    if (n == 0 || n > chunk_lanes()) return 0;
     int dev = 0, cus = 0;
     const u32* gcomb = nullptr;
     size_t C = 0;
     if (int e = device_tables(&dev, &gcomb, &cus)) return e;
     if (int e = ensure_scratch(sc, dev, n, true, &C)) return e;
-    if (n > C) return 0;
+    if (n > C) return 0;  // chunked
     const size_t eC = std::min(chunk_lanes(), (early_n + 255) & ~(size_t)255);
     if (early.dev != dev || early_n > early.chunk_cap || eC > early.chunk_cap) return 0;  // cannot map: full K_keyq
     u32* qtab = (u32*)sc.chunk;
@@ -1013,11 +1001,9 @@ int ecdsa_launch_q_mapped(SigScratch& sc, const SigScratch& early, size_t early_
 int ecdsa_launch(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x, const uint8_t* d_y,
                  const uint8_t* d_r, const uint8_t* d_s, const uint8_t* d_m, uint8_t* d_verdict,
                  size_t n, void* stream) {
-    sc.key_ready = 0;
     sc.q_ready = 0;
-    if (int e = ecdsa_launch_pre(sc, d_tag, d_x, d_y, d_s, n, stream)) return e;
+    if (int e = ecdsa_launch_pre(sc, d_s, n, stream)) return e;
     // the same split kernels as DeviceBatch::run, on one stream
-    if (int e = ecdsa_launch_key(sc, d_tag, d_x, d_y, n, stream)) return e;
     if (int e = ecdsa_launch_q(sc, d_tag, d_x, d_y, d_r, d_s, n, stream)) return e;
     return ecdsa_launch_after_pre(sc, d_tag, d_x, d_y, d_r, d_s, d_m, d_verdict, n, stream);
 }
@@ -1025,7 +1011,7 @@ int ecdsa_launch(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x, const
 int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x,
                            const uint8_t* d_y, const uint8_t* d_r, const uint8_t* d_s,
                            const uint8_t* d_m, uint8_t* d_verdict, size_t n, void* stream,
-                           void* ev_rows_read, bool verdict_and, void* ev_q_done) {
+                           bool verdict_and, void* ev_q_done) {
     const int and_mode = verdict_and ? 1 : 0;
     if (n == 0) {  // nothing to launch; the stream still joins the other one
         if (ev_q_done) BCC_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)ev_q_done, 0));
@@ -1042,7 +1028,6 @@ int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* 
     u32* state = qtab + C * QTABLE_WORDS;
     const bool q_ahead = sc.q_ready == n && n <= C;
     const size_t A = q_ahead ? sc.q_split : 0;
-    sc.key_ready = 0;
     sc.q_ready = 0;
     sc.q_split = 0;
     if (q_ahead && A && A < n) {
@@ -1081,7 +1066,6 @@ int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* 
         BCC_HIP_TRY(hipGetLastError());
     }
     if (q_ahead) {
-        if (ev_rows_read) BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_rows_read, sm));
         const size_t T = std::max<size_t>((n + FIN_PER_THREAD - 1) / FIN_PER_THREAD, std::min<size_t>(n, (size_t)cus * 256));
         hipLaunchKernelGGL(twist_fin_kernel<false>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
                            sm, state, qtab, d_verdict, 0, n, T, and_mode);
@@ -1096,8 +1080,6 @@ int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* 
                            dim3(256), 0, sm, d_tag, d_x, d_y, d_r, d_s, d_m, sinv, base,
                            cnt, qtab, state);
         BCC_HIP_TRY(hipGetLastError());
-        if (ev_rows_read && base + cnt >= n)
-            BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_rows_read, sm));
         hipLaunchKernelGGL(twist_ladder_kernel<false>,
                            dim3((unsigned)((cnt + TLADDER_WG - 1) / TLADDER_WG)),
                            dim3(TLADDER_WG), 0, sm, state, qtab, gcomb, cnt);

@@ -129,54 +129,6 @@ __device__ __forceinline__ uint32_t addc(uint32_t x, uint32_t y, uint32_t cin, u
     return __builtin_addc(x, y, cin, &cout);
 }
 
-// r = t mod p (weak, < 2^256) with 2^256 == 2^32 + 977: s = t_hi * 977 as a chain of
-// v_mad_u64_u32 whose 64-bit addend is the previous product's high word (p >> 32: one move into a
-// zero-high pair, no 64-bit add), then x = t_lo + s + (t_hi << 32) as two carry chains, then the
-// top (< 2^34) folded once more; the rare wrap past 2^256 runs behind a branch.  (A per-limb asm
-// carry-chain reduction with SGPR carries measured 4-6 % slower in the ladder: profiles/r02/
-// ab_field_reduction_sqrtail.txt.)
-__device__ __forceinline__ void fe_reduce512_v3(uint32_t (&r)[8], const uint32_t (&t)[16]) {
-    uint32_t s[9];
-    uint64_t p = (uint64_t)t[8] * 977u;
-    s[0] = (uint32_t)p;
-#pragma unroll
-    for (int i = 1; i < 8; i++) {
-        p = (uint64_t)t[8 + i] * 977u + (p >> 32);
-        s[i] = (uint32_t)p;
-    }
-    s[8] = (uint32_t)(p >> 32);
-    uint32_t x[9], ca, cb;
-    x[0] = addc(t[0], s[0], 0, ca);
-    x[1] = addc(t[1], s[1], ca, ca);
-    x[1] = addc(x[1], t[8], 0, cb);
-#pragma unroll
-    for (int i = 2; i < 8; i++) {
-        x[i] = addc(t[i], s[i], ca, ca);
-        x[i] = addc(x[i], t[7 + i], cb, cb);
-    }
-    uint32_t dz;
-    x[8] = addc(s[8], t[15], ca, ca);
-    uint32_t x9 = addc(0u, 0u, ca, dz);  // the carries as values by add-with-carry (no selects)
-    x[8] = addc(x[8], 0, cb, cb);
-    x9 = addc(x9, 0u, cb, dz);           // top = x8 + x9 2^32 < 2^34
-    uint64_t f = (uint64_t)x[8] * 977u + x[0];
-    r[0] = (uint32_t)f;
-    uint32_t c2;
-    uint64_t f1 = (uint64_t)x[1] + x[8] + (f >> 32) + (uint64_t)x9 * 977u;  // < 2^34
-    r[1] = (uint32_t)f1;
-    uint32_t carry = (uint32_t)(f1 >> 32) + x9;  // into limb 2, small
-    r[2] = addc(x[2], carry, 0, c2);
-#pragma unroll
-    for (int i = 3; i < 8; i++) r[i] = addc(x[i], 0, c2, c2);
-    if (c2) {  // wrapped past 2^256 (rare): add 2^32 + 977 once more, cannot carry again
-        uint32_t c3;
-        r[0] = addc(r[0], 977u, 0, c3);
-        r[1] = addc(r[1], 1u, c3, c3);
-#pragma unroll
-        for (int i = 2; i < 8; i++) r[i] = addc(r[i], 0, c3, c3);
-    }
-}
-
 // A lane-mask bit (an SGPR pair written as a carry-out) as 0 / 1 in this lane.
 __device__ __forceinline__ uint32_t lane_bit(uint64_t m) {
     uint32_t v;
@@ -188,9 +140,9 @@ __device__ __forceinline__ uint32_t lane_bit(uint64_t m) {
 // v_mad_u64_u32, D_k = t[k+8] * 977 + {t[k], t[k+8]} = t[k] + t[k+8] (2^32 + 977) at limb k, so
 // the fold's two carry chains (lo + s and + hi << 32) become one chain over the overlapping D_k;
 // the top word w8 folds by one more v_mad_u64_u32 over {w0, w1 + w8}.  The common path is
-// 8 + 1 multiply-adds and 10 carry ops (fe_reduce512_v3: 9 + 25, plus 11 moves and the
-// six-limb carry walk of its top fold).  What the common path drops is flagged in SGPR carry
-// masks and added back behind one wave-uniform branch:
+// 8 + 1 multiply-adds and 10 carry ops (the two-chain reduction it replaced: 9 + 25, plus 11
+// moves and the six-limb carry walk of its top fold).  What the common path drops is flagged in
+// SGPR carry masks and added back behind one wave-uniform branch:
 //   e_k  D_k >= 2^64 (t[k+8] > 2^32 - 978: p ~ 2^-22 per limb)          -> limb k + 2
 //   c9   the chain's carry out of w8 (needs t[15] ~ 2^32 - 1)             -> limb 9
 //   ef   the top fold's carry out of limbs 0..1 (w1 + w8 ~ 2^32 - 1)      -> limb 2

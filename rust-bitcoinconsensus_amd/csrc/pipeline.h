@@ -456,7 +456,6 @@ struct SigScratch {
     void* chunk = nullptr;
     size_t chunk_cap = 0;  // lanes
     size_t chunk_short = 0;  // a chunk request the device could not hold (served by chunk_cap)
-    size_t key_ready = 0;  // tuples whose key half of the prep ran ahead (ecdsa_launch_key)
     size_t q_ready = 0;    // tuples whose Q ladder ran ahead (ecdsa_launch_q)
     void* qtab2 = nullptr;  // the Q tables of K_keyq's latency mode (two lanes per tuple)
     size_t qtab2_cap = 0;   // lanes
@@ -476,23 +475,37 @@ struct SigScratch {
 
 // Asynchronous launches of the ECDSA / BIP340 kernels on `stream` with caller-owned scratch
 // (grown here when needed; growing synchronises the device).  Return 0 or a hipError_t value.
+// ecdsa_launch is the three parts below (pre, q, after_pre) on one stream.  The kernels each part
+// launches, per path (ecdsa_verify.hip's header has what each computes):
+// split path, n fits one scratch chunk:
+//   pre        batch_sinv_kernel           K_inv; its one inversion per thread is safegcd (sc_inv)
+//   q          keyq_copy_kernel            only ecdsa_launch_q_mapped with early twins
+//   q          twist_keyq_kernel           K_keyq (twice for a residency tail), or
+//              twist_keyq2_kernel          its latency mode for a small round
+//   after_pre  twist_ladder_g_kernel       the G ladder (twice after a split K_keyq)
+//   after_pre  twist_fin_kernel<false>     K_tfin
+// chunked path, n above the scratch chunk (q launches nothing):
+//   pre        batch_sinv_kernel           K_inv
+//   after_pre  ecdsa_tprep_kernel          per chunk
+//   after_pre  twist_ladder_kernel<false>  per chunk
+//   after_pre  twist_fin_kernel<false>     per chunk
+// BIP340 (schnorr_launch), per chunk:
+//              schnorr_tladder_kernel      prep + ladder
+//              twist_fin_kernel<true>      K_tfin
 int ecdsa_launch(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x, const uint8_t* d_y,
                  const uint8_t* d_r, const uint8_t* d_s, const uint8_t* d_m, uint8_t* d_verdict,
                  size_t n, void* stream);
-// The same in two parts: K_inv + K_key (s^-1 and the pubkey parse / decompression read only the
-// s and key rows, so they can run beside the sighash kernels on another stream) and everything
-// after them (must be ordered after both, and after the sighash kernels that write m).
-int ecdsa_launch_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x,
-                     const uint8_t* d_y, const uint8_t* d_s, size_t n, void* stream);
-// The message-free part of the ECDSA lane ahead of the sighash kernels, in one launch
-// (twist_keyq_kernel): the key half of the prep (key parse without a square root, the co-Z Q_w
-// table), the r / s half (u2 = r s^-1, GLV split) and the Q ladder B = u2 Q_w, on `stream` after
-// K_inv (ecdsa_launch_pre for the same n, ordered before it).  ecdsa_launch_key marks the round
-// (no launch; it may be called from any stream); the next ecdsa_launch_after_pre for the same n
-// then forms u1 from the sighash rows and runs only the G ladder, the combine and K_tfin.  Both
-// are no-ops (return 0) when n does not fit one scratch chunk (the chunked path preps per chunk).
-int ecdsa_launch_key(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x, const uint8_t* d_y,
-                     size_t n, void* stream);
+// K_inv (batch_sinv_kernel): s^-1 of every tuple.  It reads only the s rows, so it can run beside
+// the sighash kernels on another stream.
+int ecdsa_launch_pre(SigScratch& sc, const uint8_t* d_s, size_t n, void* stream);
+// K_keyq: the message-free part of the ECDSA lane ahead of the sighash kernels, in one launch
+// (twist_keyq_kernel; two launches for the residency tail, SigScratch::q_split;
+// twist_keyq2_kernel for a small round): the key half of the prep (key parse without a square
+// root, the co-Z Q_w table), the r / s half (u2 = r s^-1, GLV split) and the Q ladder
+// B = u2 Q_w, on `stream` after K_inv (ecdsa_launch_pre for the same n, ordered before it).  It
+// sets SigScratch::q_ready; the next ecdsa_launch_after_pre for the same n then forms u1 from the
+// sighash rows and runs only the G ladder, the combine and K_tfin.  A no-op (return 0) when n
+// does not fit one scratch chunk: the chunked path preps per chunk in ecdsa_launch_after_pre.
 int ecdsa_launch_q(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x, const uint8_t* d_y,
                    const uint8_t* d_r, const uint8_t* d_s, size_t n, void* stream);
 // The same for rows that may have an early twin (TupleRows::emap, device copy d_emap): a mapped
@@ -502,9 +515,9 @@ int ecdsa_launch_q_mapped(SigScratch& sc, const SigScratch& early, size_t early_
                           const uint32_t* d_emap, const uint8_t* d_tag, const uint8_t* d_x,
                           const uint8_t* d_y, const uint8_t* d_r, const uint8_t* d_s, size_t n,
                           void* stream);
-// ev_rows_read (optional hipEvent_t) is recorded on `stream` once the last kernel that reads the
-// s / m / key rows and the s^-1 rows has been launched (the prep kernel): later writers of those
-// rows (the next run's front kernels) need only wait for it, not for the ladder.
+// Everything after K_inv and K_keyq (ordered after both, and after the sighash kernels that write
+// m).  Split path (q_ready == n): twist_ladder_g_kernel, twist_fin_kernel<false>.  Chunked path,
+// per chunk: ecdsa_tprep_kernel, twist_ladder_kernel<false>, twist_fin_kernel<false>.
 // verdict_and: the caller has set d_verdict[0, n) to 1 (and may already have cleared rows, e.g.
 // the key-hash conditions); K_tfin then only clears the rows that fail.
 // ev_q_done (optional hipEvent_t): recorded after the Q launches on another stream; `stream`
@@ -513,8 +526,7 @@ int ecdsa_launch_q_mapped(SigScratch& sc, const SigScratch& early, size_t early_
 int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x,
                            const uint8_t* d_y, const uint8_t* d_r, const uint8_t* d_s,
                            const uint8_t* d_m, uint8_t* d_verdict, size_t n, void* stream,
-                           void* ev_rows_read = nullptr, bool verdict_and = false,
-                           void* ev_q_done = nullptr);
+                           bool verdict_and = false, void* ev_q_done = nullptr);
 int schnorr_launch(SigScratch& sc, const uint8_t* d_sig64, const uint8_t* d_msg32,
                    const uint8_t* d_xonly32, uint8_t* d_verdict, size_t n, void* stream);
 

@@ -181,36 +181,18 @@ BCC_HD void fe_reduce512(fe& r, const u32 (&t)[16]) {
     }
 }
 
-// Device builds use the inline-asm column products (fe_asm_gen.h) and fe_reduce512_v3 (fe_asm.h:
-// the 977-products chained through their high words, two carry chains for the rest; 4.4 % fewer
-// VALU instructions in the ladder than the round-1 reduction, profiles/r02tw4/ab_summary.txt);
+// Device builds use the inline-asm column products (fe_asm_gen.h) and fe_reduce512_v4 (fe_asm.h:
+// one multiply-add per limb pair, one carry chain, the rare carries behind a wave-uniform branch);
 // host builds use 4 x 64-bit limbs (below) or the portable formulation above.  All compute the
-// same weak residue class.  Round 5: fe_reduce512_v4 (fe_asm.h: one multiply-add per limb pair,
-// one carry chain, the rare carries behind a wave-uniform branch); BCC_RED_V4=0 keeps v3.
-#ifndef BCC_RED_V4
-#define BCC_RED_V4 1
-#endif
+// same weak residue class.  (Earlier rounds' two-chain reduction and carry-flagged columns were
+// measured slower and are gone: DESIGN.md 3.9 - 3.11.)
 // (Round 6 also replaced v4's e_k / c9 masks by a precheck of the high limbs -- all <= 2^32 - 979
 // rule them out -- and measured it slower: the max over eight limbs sits on the reduction's
 // critical path, C2 117.1 -> 114.5 M/s, profiles/r06/ab/reduction_precheck.txt.  Not kept.)
-#if BCC_RED_V4
-#define BCC_FE_REDUCE fe_reduce512_v4
-#else
-#define BCC_FE_REDUCE fe_reduce512_v3
-#endif
-// Round 5: the product columns' first multiply-adds unguarded, their rare carries flagged
-// (fe_asm_gen.h mul_256x256_col_f / sqr_cross_col_f); a wave with a flagged lane redoes the product
-// with the exact columns.  BCC_MUL_FLAG=0 keeps the exact columns only.
-#ifndef BCC_MUL_FLAG
-#define BCC_MUL_FLAG 1
-#endif
-// Round 6: no flags at all.  The columns' first carries are provably zero when a[0] and b[7] (a[0]
-// and a[7] for a square) are at most 2^32 - 9 (tools/gen_fe_asm.py, mul_256x256_col_u); one
-// compare per operand and a wave-wide ballot pick the unguarded columns or, when any lane has such
-// a limb, the exact ones.  BCC_MUL_PRECHECK=0 keeps round 5's flags.
-#ifndef BCC_MUL_PRECHECK
-#define BCC_MUL_PRECHECK 1
-#endif
+// The product columns' first carries are provably zero when a[0] and b[7] (a[0] and a[7] for a
+// square) are at most 2^32 - 9 (tools/gen_fe_asm.py, mul_256x256_col_u); one compare per operand
+// and a wave-wide ballot pick the unguarded columns or, when any lane has such a limb, the exact
+// ones.
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ bool any_lane_top_limbs(u32 lo_limb, u32 hi_limb) {
     return __builtin_amdgcn_ballot_w64((lo_limb > 0xFFFFFFF7u) | (hi_limb > 0xFFFFFFF7u)) != 0;
@@ -281,17 +263,9 @@ BCC_HD void fe_mul(fe& r, const fe& a, const fe& b) {
 #else
     u32 t[16];
 #if defined(__HIP_DEVICE_COMPILE__)
-#if BCC_MUL_PRECHECK
     if (__builtin_expect(any_lane_top_limbs(a.v[0], b.v[7]), 0)) mul_256x256_col(t, a.v, b.v);
     else mul_256x256_col_u(t, a.v, b.v);
-#elif BCC_MUL_FLAG
-    uint64_t ovf;
-    mul_256x256_col_f(t, a.v, b.v, ovf);
-    if (__builtin_expect(ovf != 0, 0)) mul_256x256_col(t, a.v, b.v);
-#else
-    mul_256x256_col(t, a.v, b.v);
-#endif
-    BCC_FE_REDUCE(r.v, t);
+    fe_reduce512_v4(r.v, t);
 #else
     mul_256x256(t, a.v, b.v);
     fe_reduce512(r, t);
@@ -305,7 +279,6 @@ BCC_HD void fe_sqr(fe& r, const fe& a) {
 #else
     u32 t[16];
 #if defined(__HIP_DEVICE_COMPILE__)
-#if BCC_MUL_PRECHECK
     if (__builtin_expect(any_lane_top_limbs(a.v[0], a.v[7]), 0)) {
         sqr_256_col(t, a.v);
     } else {
@@ -313,16 +286,7 @@ BCC_HD void fe_sqr(fe& r, const fe& a) {
         sqr_cross_col_u(x, a.v);
         sqr_tail_col(t, x, a.v);
     }
-#elif BCC_MUL_FLAG
-    uint64_t ovf;
-    u32 x[16];
-    sqr_cross_col_f(x, a.v, ovf);
-    if (__builtin_expect(ovf != 0, 0)) sqr_256_col(t, a.v);
-    else sqr_tail_col(t, x, a.v);
-#else
-    sqr_256_col(t, a.v);
-#endif
-    BCC_FE_REDUCE(r.v, t);
+    fe_reduce512_v4(r.v, t);
 #else
     sqr_256(t, a.v);
     fe_reduce512(r, t);
@@ -554,33 +518,17 @@ BCC_HD bool fe_sqrt(fe& r, const fe& a) {
 
 // r = a^-1 mod p (0 for a == 0): the safegcd inverse, 30-bit divstep batches on the device
 // (modinv_device.h), 62-bit variable-time batches on the host (modinv_host.h).  Round 4 replaced
-// the Fermat chain below (kept for BCC_INV_SAFEGCD=0 builds, the A/B baseline): C2 ECDSA stage
-// 10.36-10.40 -> 9.99-10.01 ms, C3 staged ECDSA stage 1.41 -> 1.09 ms (profiles/r04/ab_safegcd).
-#ifndef BCC_INV_SAFEGCD
-#define BCC_INV_SAFEGCD 1
-#endif
+// the Fermat chain (a^(p-2) over fe_chain_x223) with it: C2 ECDSA stage 10.36-10.40 -> 9.99-10.01
+// ms, C3 staged ECDSA stage 1.41 -> 1.09 ms (profiles/r04/ab_safegcd).
 BCC_HD void fe_inv(fe& r, const fe& a) {
+    const u32 P[8] = BCC_P_LIMBS;
 #if defined(BCC_FE_HOST64)
-    const u32 P[8] = BCC_P_LIMBS;
     modinv::inverse_var(r.v, a.v, P);
-    return;
-#elif BCC_INV_SAFEGCD
-    const u32 P[8] = BCC_P_LIMBS;
+#else
     fe an = a;
     fe_normalize(an);  // weak input: the inverse wants a < p
     mi30::inverse(r.v, an.v, P, 0x2ddacacfu);
-    return;
 #endif
-    fe x223, x22, x2, t;
-    fe_chain_x223(x223, x22, x2, a);
-    fe_sqr_n(t, x223, 23);
-    fe_mul(t, t, x22);
-    fe_sqr_n(t, t, 5);
-    fe_mul(t, t, a);
-    fe_sqr_n(t, t, 3);
-    fe_mul(t, t, x2);
-    fe_sqr_n(t, t, 2);
-    fe_mul(r, t, a);
 }
 
 // big-endian 32 bytes -> limbs
@@ -833,54 +781,16 @@ BCC_HD void sc_neg(sc& r, const sc& a) {
 
 BCC_HD bool sc_is_zero(const sc& a) { return u256_is_zero(a.v); }
 
-// r = a^(n-2) mod n by a left-to-right sliding window (w = 4) over the constant exponent: the odd
-// powers a, a^3, ..., a^15 in registers, then 58 steps "square sq times, multiply by a^(2 idx + 1)"
-// (252 squarings + 58 + 7 multiplications, against 254 + 191 for plain square-and-multiply).  The
-// step list is a constant table, so every branch is wave-uniform and the power table is indexed
-// by constants only (no scratch).  The batched path (batch_sinv_kernel) amortises this.
+// r = a^-1 mod n (0 for a == 0), a < n: the safegcd inverse like fe_inv, 30-bit divstep batches on
+// the device (modinv_device.h), 62-bit variable-time batches on the host (modinv_host.h).  The
+// batched path (batch_sinv_kernel) amortises this.
 BCC_HD void sc_inv(sc& r, const sc& a) {
-#if defined(BCC_FE_HOST64)  // host builds: the variable-time safegcd inverse (modinv_host.h)
     const u32 N[8] = BCC_N_LIMBS;
+#if defined(BCC_FE_HOST64)
     modinv::inverse_var(r.v, a.v, N);
-    return;
-#elif BCC_INV_SAFEGCD  // device: the 30-bit safegcd (modinv_device.h); a < n
-    const u32 N[8] = BCC_N_LIMBS;
+#else
     mi30::inverse(r.v, a.v, N, 0x2a774ec1u);
-    return;
 #endif
-    // n - 2 = FFFFFFFF FFFFFFFF FFFFFFFF FFFFFFFE BAAEDCE6 AF48A03B BFD25E8C D036413F
-    static constexpr uint8_t SQ[58] = {0, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4,
-                                       4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 3, 5, 3, 4, 4, 5, 2, 5, 6,
-                                       5, 4, 3, 6, 10, 4, 5, 4, 5, 6, 4, 5, 6, 10, 4, 9, 4, 1};
-    static constexpr uint8_t IX[58] = {7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7,
-                                       7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 3, 5, 2, 2, 3, 6, 1, 3, 6,
-                                       5, 6, 0, 2, 3, 3, 7, 7, 4, 5, 6, 1, 6, 6, 4, 4, 7, 0};
-    sc p0 = a, p1, p2, p3, p4, p5, p6, p7, a2;
-    sc_sqr(a2, a);
-    sc_mul(p1, p0, a2);
-    sc_mul(p2, p1, a2);
-    sc_mul(p3, p2, a2);
-    sc_mul(p4, p3, a2);
-    sc_mul(p5, p4, a2);
-    sc_mul(p6, p5, a2);
-    sc_mul(p7, p6, a2);
-    sc acc = p7;  // step 0: a^15
-#pragma unroll 1
-    for (int k = 1; k < 58; k++) {
-#pragma unroll 1
-        for (int q = 0; q < SQ[k]; q++) sc_sqr(acc, acc);
-        switch (IX[k]) {
-        case 0: sc_mul(acc, acc, p0); break;
-        case 1: sc_mul(acc, acc, p1); break;
-        case 2: sc_mul(acc, acc, p2); break;
-        case 3: sc_mul(acc, acc, p3); break;
-        case 4: sc_mul(acc, acc, p4); break;
-        case 5: sc_mul(acc, acc, p5); break;
-        case 6: sc_mul(acc, acc, p6); break;
-        default: sc_mul(acc, acc, p7); break;
-        }
-    }
-    r = acc;
 }
 
 // r = round(a * g / 2^384) for 256-bit a, g (scalar_mul_shift_var semantics, shift 384)

@@ -272,23 +272,6 @@ __device__ __forceinline__ void sha256d_tpl_lane(const uint8_t* __restrict__ tpl
     o[1] = make_uint4(bswap_u32(d[4]), bswap_u32(d[5]), bswap_u32(d[6]), bswap_u32(d[7]));
 }
 
-// K1 + K3' fused: lanes [0, naux) hash the aux messages, lanes [naux, naux + ntpl) the template
-// jobs.  Neither depends on the other, so one launch overlaps the two longest serial chains of a
-// many-input tx (its hashPrevouts message and its legacy preimages) instead of running them back
-// to back.
-__global__ __launch_bounds__(64) void sha256d_aux_tpl_kernel(
-    const uint8_t* __restrict__ aux, const uint32_t* __restrict__ aux_off,
-    const uint32_t* __restrict__ aux_nblk, uint32_t naux, uint8_t* __restrict__ auxd,
-    const uint8_t* __restrict__ tpl, const uint8_t* __restrict__ code,
-    const TplJob* __restrict__ jobs, uint32_t ntpl, uint8_t* __restrict__ msg) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < naux)
-        sha256d_msg_lane(aux, aux_off, aux_nblk, i, auxd, nullptr);
-    else if (i - naux < ntpl)
-        sha256d_tpl_lane(tpl, code, jobs, i - naux, msg);
-}
-
-
 // ------------------------------------------------------------------------------------------
 // §8f rank 4: BIP143 sighashes from the raw transaction bytes (pipeline.h WtxRec / WinJob).
 // Every lane streams bytes into a SHA-256 whose 64-byte block buffer and state live in the lane's
@@ -609,15 +592,6 @@ __device__ __forceinline__ void bip143_tx_lane(const uint8_t* __restrict__ txraw
     uint4* o = reinterpret_cast<uint4*>(d + 32 * role);
     o[0] = make_uint4(bswap_u32(dd[0]), bswap_u32(dd[1]), bswap_u32(dd[2]), bswap_u32(dd[3]));
     o[1] = make_uint4(bswap_u32(dd[4]), bswap_u32(dd[5]), bswap_u32(dd[6]), bswap_u32(dd[7]));
-}
-
-__global__ __launch_bounds__(XS_WG) void bip143_tx_kernel(const uint8_t* __restrict__ txraw,
-                                                          const WtxRec* __restrict__ recs,
-                                                          uint32_t n, uint32_t* __restrict__ intab,
-                                                          uint8_t* __restrict__ txd) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[XS_WG * (XW_BYTES + 4)];
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < 3 * n) bip143_tx_lane(txraw, recs, n, g, intab, txd, lds + threadIdx.x * (XW_BYTES + 4));
 }
 
 // The whole sighash front of a round in ONE launch (round 3): K_wtx's role lanes first (a
@@ -1033,11 +1007,9 @@ int DeviceBatch::early_launch(const TupleRows* const* Rw, size_t P, const Sighas
         early_msg_ = a + o_msg;
     }
     const uint8_t *dt = a + o_tag, *dx = a + o_x, *dy = a + o_y, *dr = a + o_r, *ds = a + o_s;
-    if (int e = ecdsa_launch_pre(early_scratch_, dt, dx, dy, ds, R, es)) return e;
-    if (int e = ecdsa_launch_key(early_scratch_, dt, dx, dy, R, es)) return e;
+    if (int e = ecdsa_launch_pre(early_scratch_, ds, R, es)) return e;
     if (int e = ecdsa_launch_q(early_scratch_, dt, dx, dy, dr, ds, R, es)) return e;
     const bool launched = early_scratch_.q_ready == R;
-    early_scratch_.key_ready = 0;
     early_scratch_.q_ready = 0;
     BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_early_, es));
     early_pending_ = true;
@@ -1948,8 +1920,7 @@ int DeviceBatch::run_stages(void* stream, const LateMsgFill* late) {
     BCC_HIP_TRY(hipStreamWaitEvent(side, (hipEvent_t)ev_fork_, 0));
     if (int e = upload_on(side, st, 1)) return e;
     BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_up_, side));  // the tuple rows are on the device
-    if (int e = ecdsa_launch_pre(scratch_, d_tag, d_x, d_y, d_s, n_rows_, side)) return e;
-    if (int e = ecdsa_launch_key(scratch_, d_tag, d_x, d_y, n_rows_, side)) return e;
+    if (int e = ecdsa_launch_pre(scratch_, d_s, n_rows_, side)) return e;
     if (d_emap_ && early_n_) {  // rows with early twins: their K_keyq results are copied
         BCC_HIP_TRY(hipStreamWaitEvent(side, (hipEvent_t)ev_early_, 0));
         if (int e = ecdsa_launch_q_mapped(scratch_, early_scratch_, early_n_, d_emap_, d_tag, d_x, d_y,
@@ -1982,7 +1953,7 @@ int DeviceBatch::run_stages(void* stream, const LateMsgFill* late) {
     // (the wait for the Q launches, ev_join_, is placed by ecdsa_launch_after_pre: with a split
     // K_keyq the G ladder of the whole rounds starts before the tail round's K_keyq is done)
     return ecdsa_launch_after_pre(scratch_, d_tag, d_x, d_y, d_r, d_s, d_m, d_v, n_rows_, st,
-                                  nullptr, kh_done_, ev_join_);
+                                  kh_done_, ev_join_);
 }
 
 // Verdicts come back through a pinned buffer of the batch (an asynchronous copy on the run's stream,
