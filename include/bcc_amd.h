@@ -182,6 +182,68 @@ int bcc_taproot_spend_batch(const bcc_taproot_spend* items, size_t n, int* ret_o
  * kernels.  For tests: a small value puts round boundaries inside a small batch.  Returns 0. */
 int bcc_set_spend_round(size_t items);
 
+/* ---- any input against its spent outputs ------------------------------------------------------
+ * The block validator's one call: VerifyScript (depend/bitcoin/src/script/interpreter.cpp:
+ * 1937-2056) for input n_in of a transaction given the outputs the whole transaction spends, as
+ * later libconsensus versions take them (a serialized std::vector<CTxOut>, one per input: what
+ * PrecomputedTransactionData::Init receives, :1422-1472).  The scriptPubKey and the amount are read
+ * from spent_outputs[n_in].  Inputs that spend a native v1 program go to the engine of
+ * bcc_taproot_spend_batch, every other input to the engine of bitcoinconsensus_verify_batch, in one
+ * stable partition (adjacent items with the same tx and spent_outputs pointers keep sharing their
+ * per-tx work on either side); both run as they do under their own entry points.
+ * The item is bcc_taproot_spend's: tx, tx_len, spent_outputs, spent_outputs_len, n_in. */
+#define BCC_SCRIPT_FLAGS_VERIFY_TAPROOT (1U << 17) /* SCRIPT_VERIFY_TAPROOT (interpreter.h) */
+#define BCC_ERR_SPENT_OUTPUTS_MISMATCH 7           /* (6 is BCC_ERR_DEVICE_FAILURE) */
+typedef bcc_taproot_spend bcc_input;
+/* Per item, ret_out[i] / err_out[i] (err_out may be NULL) are decided by the first rule that
+ * applies:
+ *  1. flags.  Accepted: any subset of bitcoinconsensus_SCRIPT_FLAGS_VERIFY_ALL, or exactly
+ *     VERIFY_ALL | BCC_SCRIPT_FLAGS_VERIFY_TAPROOT (the tapscript interpreter and the Taproot
+ *     kernels stand for that one set, every block's since activation).  Anything else (TAPROOT with
+ *     an incomplete base set, any other bit): ret 0 / bitcoinconsensus_ERR_INVALID_FLAGS for every
+ *     item.
+ *  2. the transaction.  ret 0 / the error bitcoinconsensus_verify_script_with_amount writes for
+ *     this tx, tx_len and n_in whatever the script: ERR_TX_DESERIALIZE, ERR_TX_INDEX,
+ *     ERR_TX_SIZE_MISMATCH, in that order (bitcoinconsensus.cpp:79-102).
+ *  3. the spent outputs.  They must deserialize as a std::vector<CTxOut> with no byte left over and
+ *     hold as many outputs as the tx has inputs, else ret 0 / BCC_ERR_SPENT_OUTPUTS_MISMATCH, also
+ *     for an input whose own check would not read the other outputs.
+ *  4. the script.  err OK, and ret = VerifyScript(tx.vin[n_in].scriptSig,
+ *     spent_outputs[n_in].scriptPubKey, &witness, flags, checker) with the checker's amount
+ *     spent_outputs[n_in].nValue and its PrecomputedTransactionData initialised with the spent
+ *     outputs.  The script error is not reported (bcc_taproot_spend_batch reports it for v1
+ *     inputs).  Without TAPROOT a native v1 program passes unchecked, as in
+ *     bitcoinconsensus_verify_batch.  A v1 input for which bcc_taproot_spend_batch answers ret -1
+ *     after rules 1-3 (a non-empty scriptSig that meets ECDSA checks) is invalid under every
+ *     verdict: ret 0 / err OK.
+ * Returns the number of valid items (0 for n == 0), or -1 for a null items or ret_out or an item
+ * with a null tx or spent_outputs (nothing is verified then), or -1 when a device round failed:
+ * the non-v1 side follows bcc_set_device_failure_policy exactly as bitcoinconsensus_verify_batch
+ * does (its unfinished items carry BCC_ERR_DEVICE_FAILURE); the v1 side has no host path, so after
+ * its failure no output is meaningful.  Both sides use the devices of bcc_set_device /
+ * bcc_set_devices.  Results never depend on the device set, bcc_set_pipeline_chunk,
+ * bcc_set_spend_round or the thread count.  Synchronous.  A call with items for both sides runs them
+ * at the same time: the non-v1 subset on the calling thread, the v1 subset on a second thread that
+ * the calling thread keeps as its own concurrent caller (its team and device state are released by
+ * the calling thread's bcc_release_thread_state, and it is joined when the calling thread exits). */
+long bcc_verify_inputs_batch(const bcc_input* items, size_t n, unsigned int flags, int* ret_out,
+                             int* err_out);
+/* One input: ret, and *err when err != NULL.  A null tx or spent_outputs counts as an empty buffer.
+ * Where the batch call would return -1 for a failed device round there is no verdict, and the call
+ * aborts as bitcoinconsensus_verify_script_with_amount does. */
+int bcc_verify_input(const unsigned char* tx, unsigned int tx_len,
+                     const unsigned char* spent_outputs, unsigned int spent_outputs_len,
+                     unsigned int n_in, unsigned int flags, int* err);
+typedef struct bcc_inputs_stats {
+    /* items = ecdsa_side_items + taproot_side_items + host_decided_items (rules 1-3) */
+    size_t items, ecdsa_side_items, taproot_side_items, host_decided_items;
+    /* the routing pass (rules 1-3, locating spent[n_in], the partition), each side's call (the two
+     * overlap when both sides have items, so they do not add up to the total), the whole call */
+    double route_seconds, ecdsa_side_seconds, taproot_side_seconds, total_seconds;
+} bcc_inputs_stats;
+/* Statistics of the calling thread's last bcc_verify_inputs_batch / bcc_verify_input call. */
+void bcc_last_inputs_stats(bcc_inputs_stats* out);
+
 /* The layer below (the role mi_schnorr_verify_tuples has for signatures): n rows of the tweaked
  * key q, the parity byte, the internal key p and the tweak t (32-byte big-endian strings).
  * verdict[i] = 1 iff secp256k1_xonly_pubkey_parse(internal32_i) succeeds and

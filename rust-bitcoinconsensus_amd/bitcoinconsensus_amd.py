@@ -7,6 +7,8 @@ This is the host-side surface a user of the reference crate switches to:
     height_to_flags(height), version()                                   src/lib.rs:45-68
     VERIFY_* constants, Error enum                                       src/lib.rs:22-42, 164-185
     verify_batch([...])  -- new: N independent verify() calls, signature work on the GPU
+    verify_inputs_batch([...])  -- new: any input (v1 included) against the outputs its tx spends,
+                                   flag VERIFY_TAPROOT accepted (include/bcc_amd.h)
 
 plus the inner tuple ABI ``ecdsa_verify_tuples`` and device-pointer entry points
 used by bench.py.  Every call goes to librbc_amd.so (HIP kernels for gfx950); if the library is
@@ -780,6 +782,110 @@ def set_spend_round(items, library=None):
     L = library if library is not None else lib()
     L.bcc_set_spend_round.argtypes = [ctypes.c_size_t]
     L.bcc_set_spend_round(items)
+
+
+VERIFY_TAPROOT = 1 << 17  # include/bcc_amd.h BCC_SCRIPT_FLAGS_VERIFY_TAPROOT
+ERR_SPENT_OUTPUTS_MISMATCH = 7  # include/bcc_amd.h BCC_ERR_SPENT_OUTPUTS_MISMATCH
+
+
+class InputsError(enum.IntEnum):
+    """The code verify_inputs_batch adds to the crate's Error: the spent outputs do not deserialize
+    or their count differs from the transaction's inputs.  Kept outside Error like DeviceFailure:
+    the crate's repr(C) enum stops at 5, and error_from_code stays the mapping of the libconsensus
+    entry points, which never write 7."""
+    ERR_SPENT_OUTPUTS_MISMATCH = ERR_SPENT_OUTPUTS_MISMATCH
+
+
+def inputs_error_from_code(code):
+    """An err_out code of bcc_verify_inputs_batch -> Error (0-5), DeviceFailure (6) or
+    InputsError.ERR_SPENT_OUTPUTS_MISMATCH (7); anything else is a ValueError."""
+    if int(code) == ERR_SPENT_OUTPUTS_MISMATCH:
+        return InputsError.ERR_SPENT_OUTPUTS_MISMATCH
+    return error_from_code(code)
+
+
+InputItem = TaprootSpend  # include/bcc_amd.h: typedef bcc_taproot_spend bcc_input
+
+
+class InputsStats(ctypes.Structure):
+    """include/bcc_amd.h bcc_inputs_stats."""
+    _fields_ = [("items", ctypes.c_size_t), ("ecdsa_side_items", ctypes.c_size_t),
+                ("taproot_side_items", ctypes.c_size_t), ("host_decided_items", ctypes.c_size_t),
+                ("route_seconds", ctypes.c_double), ("ecdsa_side_seconds", ctypes.c_double),
+                ("taproot_side_seconds", ctypes.c_double), ("total_seconds", ctypes.c_double)]
+
+
+def _bind_inputs(L):
+    ip = ctypes.POINTER(ctypes.c_int)
+    L.bcc_verify_inputs_batch.argtypes = [ctypes.POINTER(InputItem), ctypes.c_size_t, ctypes.c_uint,
+                                          ip, ip]
+    L.bcc_verify_inputs_batch.restype = ctypes.c_long
+    L.bcc_verify_input.argtypes = [ctypes.c_char_p, ctypes.c_uint, ctypes.c_char_p, ctypes.c_uint,
+                                   ctypes.c_uint, ctypes.c_uint, ip]
+    L.bcc_last_inputs_stats.argtypes = [ctypes.POINTER(InputsStats)]
+    return L
+
+
+def input_items(items):
+    """(InputItem array, keep-alive buffers) for dicts with keys tx, spent, nin.  Adjacent items
+    that pass the same tx / spent bytes objects share one buffer each (and with it the per-tx
+    work)."""
+    n = len(items)
+    arr = (InputItem * max(n, 1))()
+    keep = []
+    for i, c in enumerate(items):
+        tx, spent = bytes(c["tx"]), bytes(c["spent"])
+        if i and items[i - 1]["tx"] is c["tx"]:
+            tx = keep[-1][0]
+        if i and items[i - 1]["spent"] is c["spent"]:
+            spent = keep[-1][1]
+        keep.append((tx, spent))
+        arr[i] = InputItem(tx, len(tx), spent, len(spent), c["nin"] & 0xffffffff)
+    return arr, keep
+
+
+def verify_inputs_batch_raw(items, flags=VERIFY_ALL | VERIFY_TAPROOT, library=None):
+    """bcc_verify_inputs_batch as is: (return code, [(ret, err int)]); rc is the number of valid
+    items, or -1 when a device round failed."""
+    arr, keep = input_items(items)
+    n = len(keep)
+    ret = (ctypes.c_int * max(n, 1))()
+    err = (ctypes.c_int * max(n, 1))()
+    L = _bind_inputs(library if library is not None else lib())
+    rc = L.bcc_verify_inputs_batch(arr, n, flags & 0xffffffff, ret, err)
+    return rc, [(ret[i], err[i]) for i in range(n)]
+
+
+def verify_inputs_batch(items, flags=VERIFY_ALL | VERIFY_TAPROOT, library=None):
+    """Any input against the outputs its transaction spends (include/bcc_amd.h
+    bcc_verify_inputs_batch): an item is a dict with keys tx, spent (the serialized
+    std::vector<CTxOut> the whole tx spends, one per input) and nin.  Native v1 inputs run on the
+    Taproot engine, every other input on the engine of verify_batch, in one call.  Returns
+    [(ret, err)]: err 0 with ret = VerifyScript's verdict, or ret 0 with ERR_INVALID_FLAGS (5), a
+    transaction error (1-3) or ERR_SPENT_OUTPUTS_MISMATCH (7); inputs_error_from_code names them.
+    Raises RuntimeError when a device round failed.  `library`: another build of the same C ABI
+    (tests: the host code over the oracle stub)."""
+    rc, res = verify_inputs_batch_raw(items, flags, library)
+    if rc < 0:
+        raise RuntimeError("bcc_verify_inputs_batch: device pipeline failed")
+    return res
+
+
+def verify_input(tx, spent_outputs, input_index, flags=VERIFY_ALL | VERIFY_TAPROOT, library=None):
+    """bcc_verify_input: (ret, err) of one input, as one item of verify_inputs_batch."""
+    L = _bind_inputs(library if library is not None else lib())
+    e = ctypes.c_int(0)
+    tx, spent_outputs = bytes(tx), bytes(spent_outputs)
+    r = L.bcc_verify_input(tx, len(tx) & 0xffffffff, spent_outputs, len(spent_outputs) & 0xffffffff,
+                           input_index & 0xffffffff, flags & 0xffffffff, ctypes.byref(e))
+    return r, e.value
+
+
+def last_inputs_stats(library=None):
+    """bcc_last_inputs_stats: the calling thread's last verify_inputs_batch / verify_input call."""
+    s = InputsStats()
+    _bind_inputs(library if library is not None else lib()).bcc_last_inputs_stats(ctypes.byref(s))
+    return {k: getattr(s, k) for k, _ in InputsStats._fields_}
 
 
 def xonly_tweak_check_tuples(tweaked32, parity, internal32, tweak32, device=0):

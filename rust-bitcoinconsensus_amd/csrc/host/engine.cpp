@@ -29,6 +29,7 @@
 #include "engine.h"
 #include "hashes.h"
 #include "host_verify.h"
+#include "inputs.h"
 #include "script.h"
 #include "sighash.h"
 #include "team.h"
@@ -2177,6 +2178,7 @@ int bcc_set_pipeline_tail(size_t items) {
 
 void bcc_release_thread_state(void) {
     for (auto& c : tl_chunk) c = ChunkRun();
+    bcc::host::inputs_release_thread_state();
     bcc::host::taproot_release_thread_state();
     bcc::release_device_thread_state();
     bcc::release_tuple_thread_state();
