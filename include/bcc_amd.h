@@ -460,6 +460,36 @@ void bcc_debug_fail_device_rounds_code(int rounds, int hip_error);
  * 64k lanes) instead of failing the round. */
 void bcc_debug_scratch_cap_lanes(size_t lanes);
 
+/* Test hook (coverage only): the shape a signature batch of n rows takes on a device with `cus`
+ * compute units (cus <= 0: the current device's), computed by the helpers the launchers themselves
+ * call, without launching or allocating anything.  A thread of K_inv / K_tfin walks the chain of
+ * lanes t, t + T, t + 2 T, ... of its chunk and shares one inversion among them; *_threads is that
+ * T.  BIP340 batches take the chunk stride and the K_tfin counts only (no K_inv, no K_keyq).
+ * chunk_stride assumes the scratch fits on the device (else the launchers halve it).  Returns 0,
+ * -1 for a null `out`, or a hipError_t value when the device cannot be asked. */
+#define BCC_SHAPE_LATENCY 0    /* twist_keyq2_kernel: at most one wave per SIMD, two lanes a row */
+#define BCC_SHAPE_ONE_LAUNCH 1 /* one K_keyq launch */
+#define BCC_SHAPE_SPLIT 2      /* K_keyq as whole residency rounds [0, split_at) + a tail launch */
+#define BCC_SHAPE_CHUNKED 3    /* n above the chunk stride: prep, ladder and K_tfin per chunk */
+typedef struct bcc_launch_shape {
+    size_t mode;              /* BCC_SHAPE_* (ECDSA) */
+    size_t split_at;          /* A: first lane of the tail launch, 0 unless BCC_SHAPE_SPLIT */
+    size_t chunk_stride;      /* C */
+    size_t chunks;            /* ceil(n / C) */
+    size_t inv_threads;       /* K_inv's T, over the whole batch */
+    size_t fin_threads_first; /* K_tfin's T in the first chunk ... */
+    size_t fin_threads_last;  /* ... and in the last one */
+    size_t ladder_wg;         /* lanes per ladder workgroup */
+    size_t inv_per_thread;    /* longest K_inv chain */
+    size_t fin_per_thread;    /* longest K_tfin chain */
+    size_t cus;
+    size_t round_lanes;       /* R: lanes of one K_keyq residency round */
+} bcc_launch_shape;
+int bcc_debug_launch_shape(size_t n, int cus, bcc_launch_shape* out);
+/* The same for the commitment kernels: tweak_fin_kernel's thread count T over a chunk of cnt rows
+ * (its thread t walks lanes t, t + T, ... and shares one inversion among them). */
+size_t bcc_debug_commit_fin_threads(size_t cnt);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1050,6 +1050,41 @@ def debug_scratch_cap_lanes(lanes):
     lib().bcc_debug_scratch_cap_lanes(lanes)
 
 
+SHAPE_MODES = ("latency", "one_launch", "split", "chunked")  # BCC_SHAPE_* of bcc_amd.h
+
+
+class LaunchShape(ctypes.Structure):
+    """struct bcc_launch_shape (include/bcc_amd.h)."""
+    _fields_ = [(k, ctypes.c_size_t) for k in
+                ("mode", "split_at", "chunk_stride", "chunks", "inv_threads", "fin_threads_first",
+                 "fin_threads_last", "ladder_wg", "inv_per_thread", "fin_per_thread", "cus",
+                 "round_lanes")]
+
+
+def debug_launch_shape(n, cus=0):
+    """Test hook (coverage only): the shape a signature batch of n rows takes -- mode (one of
+    SHAPE_MODES), split point, chunk stride and the K_inv / K_tfin thread counts -- from the
+    launchers' own helpers, nothing launched (bcc_debug_launch_shape).  cus = 0: the current
+    device's compute units."""
+    s = LaunchShape()
+    L = lib()
+    L.bcc_debug_launch_shape.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(LaunchShape)]
+    rc = L.bcc_debug_launch_shape(n, cus, ctypes.byref(s))
+    if rc != 0:
+        raise RuntimeError(f"bcc_debug_launch_shape failed: {rc}")
+    d = {k: int(getattr(s, k)) for k, _ in LaunchShape._fields_}
+    d["mode"] = SHAPE_MODES[d["mode"]]
+    return d
+
+
+def debug_commit_fin_threads(cnt):
+    """Test hook (coverage only): tweak_fin_kernel's thread count over a chunk of cnt rows."""
+    L = lib()
+    L.bcc_debug_commit_fin_threads.argtypes = [ctypes.c_size_t]
+    L.bcc_debug_commit_fin_threads.restype = ctypes.c_size_t
+    return int(L.bcc_debug_commit_fin_threads(cnt))
+
+
 def set_chunk_lanes(lanes):
     """Lanes per signature-kernel launch (0 restores the default); results never depend on it."""
     lib().bcc_set_chunk_lanes(ctypes.c_size_t(lanes))

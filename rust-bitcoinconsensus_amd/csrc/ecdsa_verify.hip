@@ -45,6 +45,7 @@
 #include <memory>
 #include <string>
 
+#include "bcc_amd.h"
 #include "ecdsa_lane.h"
 #include "ecdsa_twist.h"
 #include "gpu_common.h"
@@ -792,6 +793,47 @@ static hipError_t chunk_malloc(void** p, size_t lanes) {
     return hipMalloc(p, lanes * (QTABLE_WORDS + TSTATE_WORDS) * sizeof(u32));
 }
 
+// ------------------------------------------------------------------------------------------
+// Launch shape: every routing decision of the signature stage that depends on the row count, in
+// one place.  The launchers below and bcc_debug_launch_shape both take them from here.
+// ------------------------------------------------------------------------------------------
+// Threads of a batched inversion (K_inv, K_tfin) over cnt lanes: thread t walks the chain of lanes
+// t, t+T, ... below cnt -- chains of at most per_thread lanes, but at least one wave per SIMD.
+static size_t chain_threads(size_t cnt, size_t per_thread, int cus) {
+    return std::max<size_t>((cnt + per_thread - 1) / per_thread, std::min<size_t>(cnt, (size_t)cus * 256));
+}
+
+// K_keyq or, for a round of at most one wave per SIMD at two lanes per tuple, its latency mode
+// (twist_keyq2_kernel; BCC_KEYQ2=0 keeps K_keyq).
+static const bool g_keyq2 = [] {
+    const char* e = getenv("BCC_KEYQ2");
+    return !(e && atoi(e) == 0);
+}();
+static bool keyq_latency_mode(size_t n, int cus) { return g_keyq2 && 2 * n <= (size_t)cus * 4 * 64; }
+
+// The residency tail (round 6).  K_keyq holds BCC_LADDERQ_WAVES waves per SIMD, so one residency
+// round is cus x 4 SIMDs x waves x 64 lanes (262,144 on MI355X); C2's 1M lanes are 3.81 rounds, and
+// the last 0.81-full round left ~19 % of the chip idle for a whole round (~5 % of the stage;
+// DESIGN §3.3).  Split at the last whole round, the tail round's idle slots take the G ladder of
+// the lanes before it.  Returns the split (a multiple of the group size) or 0 for none
+// (BCC_KEYQ_SPLIT=0, fewer than two rounds, or a whole number of rounds).
+static const bool g_keyq_split = [] {
+    const char* e = getenv("BCC_KEYQ_SPLIT");
+    return !(e && atoi(e) == 0);
+}();
+static size_t keyq_round_lanes(int cus) { return (size_t)cus * 4 * BCC_LADDERQ_WAVES * 64; }
+static size_t keyq_split_at(size_t n, int cus) {
+    const size_t R = keyq_round_lanes(cus);
+    if (!g_keyq_split || R == 0 || n <= R || n % R == 0) return 0;
+    return n / R * R;
+}
+
+// Lanes of chunk scratch a batch of n rows asks for: the chunk stride C unless the device cannot
+// hold it (ensure_scratch).  A batch above it takes the chunked path: no K_keyq ahead of the
+// message, the whole prep per chunk.
+static size_t chunk_stride(size_t n) { return std::min(chunk_lanes(), (n + 255) & ~(size_t)255); }
+static bool chunked_path(size_t n) { return n > chunk_stride(n); }
+
 // Grows sc to n tuples (sinv rows when with_sinv) and min(n, chunk) lanes of chunk scratch;
 // returns the chunk stride C.  When the device cannot hold the chunk (other callers' scratch, a
 // smaller GPU) the request is halved until it fits (at least 64k lanes): the launches then loop
@@ -800,7 +842,7 @@ static hipError_t chunk_malloc(void** p, size_t lanes) {
 static int ensure_scratch(SigScratch& sc, int dev, size_t n, bool with_sinv, size_t* C) {
     if (sc.dev >= 0 && sc.dev != dev) return (int)hipErrorInvalidDevice;
     sc.dev = dev;
-    const size_t want = std::min(chunk_lanes(), (n + 255) & ~(size_t)255);
+    const size_t want = chunk_stride(n);
     if (want > sc.chunk_cap && want != sc.chunk_short) {
         if (sc.chunk) BCC_HIP_TRY(hipFree(sc.chunk));
         sc.chunk = nullptr;
@@ -844,7 +886,7 @@ int ecdsa_launch_pre(SigScratch& sc, const uint8_t* d_s, size_t n, void* stream)
     if (int e = device_tables(&dev, &gcomb, &cus)) return e;
     if (int e = ensure_scratch(sc, dev, n, true, &C)) return e;
     // K_inv: chunks of <= 16 tuples, but at least one wave per SIMD
-    size_t T = std::max<size_t>((n + INV_PER_THREAD - 1) / INV_PER_THREAD, std::min<size_t>(n, (size_t)cus * 256));
+    const size_t T = chain_threads(n, INV_PER_THREAD, cus);
     hipLaunchKernelGGL(batch_sinv_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, d_s, (u32*)sc.sinv, n, T);
     BCC_HIP_TRY(hipGetLastError());
@@ -880,33 +922,11 @@ static size_t keyq_lds(size_t groups, int cus, bool two_lane = false) {
     return groups <= (size_t)cus ? (two_lane ? dyn2 : dyn1) : 0;
 }
 
-// K_keyq or, for a round of at most one wave per SIMD at two lanes per tuple, its latency mode
-// (twist_keyq2_kernel; BCC_KEYQ2=0 keeps K_keyq).
-static const bool g_keyq2 = [] {
-    const char* e = getenv("BCC_KEYQ2");
-    return !(e && atoi(e) == 0);
-}();
-// The residency tail (round 6).  K_keyq holds BCC_LADDERQ_WAVES waves per SIMD, so one residency
-// round is cus x 4 SIMDs x waves x 64 lanes (262,144 on MI355X); C2's 1M lanes are 3.81 rounds, and
-// the last 0.81-full round left ~19 % of the chip idle for a whole round (~5 % of the stage;
-// DESIGN §3.3).  Split at the last whole round, the tail round's idle slots take the G ladder of
-// the lanes before it.  Returns the split (a multiple of the group size) or 0 for none
-// (BCC_KEYQ_SPLIT=0, fewer than two rounds, or a whole number of rounds).
-static const bool g_keyq_split = [] {
-    const char* e = getenv("BCC_KEYQ_SPLIT");
-    return !(e && atoi(e) == 0);
-}();
-static size_t keyq_split_at(size_t n, int cus) {
-    const size_t R = (size_t)cus * 4 * BCC_LADDERQ_WAVES * 64;
-    if (!g_keyq_split || R == 0 || n <= R || n % R == 0) return 0;
-    return n / R * R;
-}
-
 static int launch_keyq(SigScratch& sc, int cus, const uint8_t* d_tag, const uint8_t* d_x,
                        const uint8_t* d_y, const uint8_t* d_r, const uint8_t* d_s, size_t n,
                        u32* qtab, u32* state, const u32* emap, size_t ecount, hipStream_t st) {
     sc.q_split = 0;
-    if (g_keyq2 && 2 * n <= (size_t)cus * 4 * 64) {
+    if (keyq_latency_mode(n, cus)) {
         if (2 * n > sc.qtab2_cap) {
             if (sc.qtab2) BCC_HIP_TRY(hipFree(sc.qtab2));
             sc.qtab2 = nullptr;
@@ -952,7 +972,7 @@ static int launch_keyq(SigScratch& sc, int cus, const uint8_t* d_tag, const uint
 int ecdsa_launch_q(SigScratch& sc, const uint8_t* d_tag, const uint8_t* d_x, const uint8_t* d_y,
                    const uint8_t* d_r, const uint8_t* d_s, size_t n, void* stream) {
     sc.q_ready = 0;
-    if (n == 0 || n > chunk_lanes()) return 0;
+    if (n == 0 || chunked_path(n)) return 0;
     int dev = 0, cus = 0;
     const u32* gcomb = nullptr;
     size_t C = 0;
@@ -975,14 +995,14 @@ int ecdsa_launch_q_mapped(SigScratch& sc, const SigScratch& early, size_t early_
     if (!d_emap || early_n == 0 || !early.chunk)
         return ecdsa_launch_q(sc, d_tag, d_x, d_y, d_r, d_s, n, stream);
     sc.q_ready = 0;
-    if (n == 0 || n > chunk_lanes()) return 0;
+    if (n == 0 || chunked_path(n)) return 0;
     int dev = 0, cus = 0;
     const u32* gcomb = nullptr;
     size_t C = 0;
     if (int e = device_tables(&dev, &gcomb, &cus)) return e;
     if (int e = ensure_scratch(sc, dev, n, true, &C)) return e;
     if (n > C) return 0;  // chunked
-    const size_t eC = std::min(chunk_lanes(), (early_n + 255) & ~(size_t)255);
+    const size_t eC = chunk_stride(early_n);
     if (early.dev != dev || early_n > early.chunk_cap || eC > early.chunk_cap) return 0;  // cannot map: full K_keyq
     u32* qtab = (u32*)sc.chunk;
     u32* state = qtab + C * QTABLE_WORDS;
@@ -1066,7 +1086,7 @@ int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* 
         BCC_HIP_TRY(hipGetLastError());
     }
     if (q_ahead) {
-        const size_t T = std::max<size_t>((n + FIN_PER_THREAD - 1) / FIN_PER_THREAD, std::min<size_t>(n, (size_t)cus * 256));
+        const size_t T = chain_threads(n, FIN_PER_THREAD, cus);
         hipLaunchKernelGGL(twist_fin_kernel<false>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
                            sm, state, qtab, d_verdict, 0, n, T, and_mode);
         BCC_HIP_TRY(hipGetLastError());
@@ -1085,7 +1105,7 @@ int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* 
                            dim3(TLADDER_WG), 0, sm, state, qtab, gcomb, cnt);
         BCC_HIP_TRY(hipGetLastError());
         // the batched beta inversion: sub-chunks of <= 16 lanes, at least one wave per SIMD
-        const size_t T = std::max<size_t>((cnt + FIN_PER_THREAD - 1) / FIN_PER_THREAD, std::min<size_t>(cnt, (size_t)cus * 256));
+        const size_t T = chain_threads(cnt, FIN_PER_THREAD, cus);
         hipLaunchKernelGGL(twist_fin_kernel<false>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
                            sm, state, qtab, d_verdict, base, cnt, T, and_mode);
         BCC_HIP_TRY(hipGetLastError());
@@ -1110,7 +1130,7 @@ int schnorr_launch(SigScratch& sc, const uint8_t* d_sig64, const uint8_t* d_msg3
                            dim3((unsigned)((cnt + TLADDER_WG - 1) / TLADDER_WG)), dim3(TLADDER_WG),
                            0, sm, d_sig64, d_msg32, d_xonly32, base, cnt, qtab, state, gcomb);
         BCC_HIP_TRY(hipGetLastError());
-        const size_t T = std::max<size_t>((cnt + FIN_PER_THREAD - 1) / FIN_PER_THREAD, std::min<size_t>(cnt, (size_t)cus * 256));
+        const size_t T = chain_threads(cnt, FIN_PER_THREAD, cus);
         hipLaunchKernelGGL(twist_fin_kernel<true>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
                            sm, state, qtab, d_verdict, base, cnt, T, 0);
         BCC_HIP_TRY(hipGetLastError());
@@ -1313,4 +1333,36 @@ int mi_ecdsa_verify_tuples(const uint8_t* pub65, const uint8_t* msg32, const uin
 
 extern "C" void bcc_debug_scratch_cap_lanes(size_t lanes) {
     g_scratch_cap.store(lanes, std::memory_order_relaxed);
+}
+
+// The shape a batch of n rows takes (bcc_amd.h): the launchers' own helpers, nothing launched or
+// allocated.  cus <= 0 asks the current device.
+extern "C" int bcc_debug_launch_shape(size_t n, int cus, bcc_launch_shape* out) {
+    if (!out) return -1;
+    if (cus <= 0) {
+        int dev = 0;
+        BCC_HIP_TRY(hipGetDevice(&dev));
+        BCC_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    }
+    bcc_launch_shape s{};
+    s.cus = (size_t)cus;
+    s.round_lanes = keyq_round_lanes(cus);
+    s.ladder_wg = TLADDER_WG;
+    s.inv_per_thread = INV_PER_THREAD;
+    s.fin_per_thread = FIN_PER_THREAD;
+    if (n) {
+        const size_t C = chunk_stride(n);
+        s.chunk_stride = C;
+        s.chunks = (n + C - 1) / C;
+        const size_t last = n - (s.chunks - 1) * C;
+        s.inv_threads = chain_threads(n, INV_PER_THREAD, cus);
+        s.fin_threads_first = chain_threads(std::min(C, n), FIN_PER_THREAD, cus);
+        s.fin_threads_last = chain_threads(last, FIN_PER_THREAD, cus);
+        if (chunked_path(n)) s.mode = BCC_SHAPE_CHUNKED;
+        else if (keyq_latency_mode(n, cus)) s.mode = BCC_SHAPE_LATENCY;
+        else if ((s.split_at = keyq_split_at(n, cus)) != 0) s.mode = BCC_SHAPE_SPLIT;
+        else s.mode = BCC_SHAPE_ONE_LAUNCH;
+    }
+    *out = s;
+    return 0;
 }

@@ -37,6 +37,8 @@ namespace {
 
 // lanes whose R.z share one inversion (one thread of K_tfin walks lanes t, t + T, t + 2T, ...)
 constexpr size_t COMMIT_INV_GROUP = 16;
+// K_tfin's thread count T over a chunk of cnt lanes (curve_launch, bcc_debug_commit_fin_threads)
+size_t commit_fin_threads(size_t cnt) { return (cnt + COMMIT_INV_GROUP - 1) / COMMIT_INV_GROUP; }
 // K_tadd -> K_tfin scratch, word-major (word w of lane i at [w * stride + i]: coalesced):
 // X, Y, Z of R, the group's running product before the lane, the lane's status
 constexpr int S_X = 0, S_Y = 8, S_Z = 16, S_PRE = 24, S_STAT = 32, SCRATCH_WORDS = 33;
@@ -216,7 +218,7 @@ int curve_launch(const uint8_t* d_p, const uint8_t* d_q, const uint8_t* d_par, c
     if (int e = comb_device_tables(&dev, &gcomb, &cus)) return e;
     for (size_t base = 0; base < n; base += stride) {
         const size_t cnt = std::min(stride, n - base);
-        const size_t T = (cnt + COMMIT_INV_GROUP - 1) / COMMIT_INV_GROUP;
+        const size_t T = commit_fin_threads(cnt);
         kt.begin(KT_ADD);
         hipLaunchKernelGGL(tweak_add_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st,
                            d_p + 32 * base, d_q + 32 * base, d_par + base, d_t + 32 * base, d_scratch,
@@ -561,5 +563,7 @@ int bcc_taproot_commit_batch(const bcc_taproot_commit* items, size_t n, int* ret
 void bcc_commit_last_kernel_ms(double* ms3) {
     for (int k = 0; k < KT_KERNELS; k++) ms3[k] = tl_kernel_ms[k];
 }
+
+size_t bcc_debug_commit_fin_threads(size_t cnt) { return commit_fin_threads(cnt); }
 
 }  // extern "C"

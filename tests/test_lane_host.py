@@ -389,6 +389,15 @@ def test_lane_twist_structured_scalars(lane, fn):
     assert not bad, (len(bad), bad[:10])
 
 
+def test_lane_schnorr_exceptional(arith):
+    """tests/golden/schnorr_exceptional.npz through both host builds of the lane code: s = +-e d
+    takes schnorr_twist_exceptional through x(A) == x(B) (R at infinity, the doubling)."""
+    from fixtures import schnorr_exceptional
+    bad = [(i, t["cls"], t["verdict"]) for i, t in enumerate(schnorr_exceptional())
+           if arith.lane_schnorr_verify_twist(t["sig"], t["msg"], t["pub"]) != t["verdict"]]
+    assert not bad, (len(bad), bad[:10])
+
+
 def test_lane_schnorr_structured_scalars(lane):
     from fixtures import structured_scalars
     bad = [(i, t["cls"], t["verdict"]) for i, t in enumerate(structured_scalars()["schnorr"])

@@ -38,6 +38,23 @@ def test_oracle_schnorr_tuples_match_reference_verdicts():
     assert not bad, bad[:10]
 
 
+def test_oracle_schnorr_exceptional_match_reference_verdicts():
+    """s = +-e d (R at infinity, the doubling sum), their neighbours and the valid rows beside
+    them; the file holds what its generator promises."""
+    from fixtures import schnorr_exceptional
+    ts, h = schnorr_exceptional(with_header=True)
+    counts = {}
+    for t in ts:
+        counts[t["cls"]] = counts.get(t["cls"], 0) + 1
+    assert counts == h["counts"] and len(ts) == h["rows"] >= 300
+    assert counts["s_eq_ed"] >= 50 and counts["s_eq_minus_ed"] >= 50
+    assert sum(t["verdict"] for t in ts) == h["valid"] == counts["valid_same_key"]
+    assert all(t["verdict"] == (t["cls"] == "valid_same_key") for t in ts)
+    bad = [(t["cls"], i) for i, t in enumerate(ts)
+           if O.schnorr_verify(t["sig"], t["msg"], t["pub"]) != t["verdict"]]
+    assert not bad, bad[:10]
+
+
 def test_oracle_taproot_checks_match_reference():
     """BIP341 SignatureHashSchnorr + CheckSchnorrSignature restatement vs the reference's
     (ret, serror, sighash) on every committed case (make_taproot_fixtures.py)."""

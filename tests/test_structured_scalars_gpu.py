@@ -19,7 +19,8 @@ import random
 
 import pytest
 
-from fixtures import bip340_vectors, ecdsa_tuples, pub_to_tuple, schnorr_tuples, structured_scalars
+from fixtures import (bip340_vectors, ecdsa_tuples, pub_to_tuple, schnorr_exceptional, schnorr_tuples,
+                      structured_scalars)
 from oracle_ctypes import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -145,11 +146,12 @@ def test_large_batch_pubkey_verify_batch(ecdsa_rows, large, large_one_chunk):
 
 
 def test_schnorr_one_and_three_chunks():
-    """Path 5: BIP340 rows (structured keys / nonces / s, schnorr_tuples.npz, the BIP340 vectors)
-    among valid rows, in one schnorr_tladder_kernel launch and in three."""
+    """Path 5: BIP340 rows (structured keys / nonces / s, schnorr_tuples.npz, the BIP340 vectors,
+    the s = +-e d rows of schnorr_exceptional.npz) among valid rows, in one schnorr_tladder_kernel
+    launch and in three."""
     import bitcoinconsensus_amd as B
     old = schnorr_tuples()
-    rows = structured_scalars()["schnorr"] + old + bip340_vectors()
+    rows = structured_scalars()["schnorr"] + old + bip340_vectors() + schnorr_exceptional()
     fill = [t for t in old if t["cls"] == "valid" and t["verdict"] == 1]
     assert len(rows) > 2000 and len(fill) >= 300
     lanes = 1280
