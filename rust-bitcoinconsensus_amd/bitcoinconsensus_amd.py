@@ -544,6 +544,22 @@ def set_direct_upload(on):
     L.bcc_set_direct_upload(1 if on else 0)
 
 
+def set_pre_upload(on):
+    """bcc_set_pre_upload: a pipelined chunk's rows go to HBM per shard while the host pass still
+    runs (default on).  Results never depend on it."""
+    L = lib()
+    L.bcc_set_pre_upload.argtypes = [ctypes.c_int]
+    L.bcc_set_pre_upload(1 if on else 0)
+
+
+def set_fused_pass(on):
+    """bcc_set_fused_pass: the first interpreter pass runs inside the parse pass (default on).
+    Results never depend on it."""
+    L = lib()
+    L.bcc_set_fused_pass.argtypes = [ctypes.c_int]
+    L.bcc_set_fused_pass(1 if on else 0)
+
+
 def set_pipeline_chunk(items):
     """bcc_set_pipeline_chunk: verify_batch overlaps chunk k's device round with chunk k+1's host
     pass (0 disables)."""

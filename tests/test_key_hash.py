@@ -5,6 +5,11 @@ another program — only the key-hash check can reject them (the reference stops
 interpreter.cpp:871-884 for P2PKH, :1936-1945 for P2WPKH) — beside the same spends with the right
 program, for P2WPKH, P2SH-P2WPKH and P2PKH with compressed, uncompressed and hybrid keys.
 
+The wrong program here is always the hash of another key, so all 20 bytes differ: a comparison
+that skipped a word or a byte would still pass.  The key-hash family of
+tests/golden/rerun_cases.json.gz (tests/rerun_cases.py, test_rerun_host.py / test_rerun_gpu.py)
+closes that: the same nine shapes with each of the 160 program bits flipped in turn.
+
 Verdicts come from the reference library (oracle/_ref) on the same items.  CPU: the engine's host
 logic with the stub device (tests/native/engine_host_stub.cpp applies the rows' key-hash
 conditions the way the kernel does); GPU: librbc_amd.so."""
