@@ -358,6 +358,15 @@ int bcc_set_early_q(int on);
  * Results never depend on it. */
 int bcc_set_device_key_hash(int on);
 
+/* The remaining ECDSA-era hash types on the device-assembled paths: legacy NONE / SINGLE /
+ * ANYONECANPAY checks (and their combinations) and BIP143 SIGHASH_SINGLE checks become device jobs
+ * built from the raw transaction, which is uploaded once per round, instead of one host-serialized
+ * preimage per check (O(inputs^2) bytes for a legacy transaction).  Default 0, or the
+ * BCC_DEVICE_HASHTYPES environment variable: 0 keeps the host preimage path for them.  The
+ * bcc_set_host_chain_blocks offload of long legacy chains applies either way.  Results never
+ * depend on it.  Returns 0. */
+int bcc_set_device_hashtypes(int on);
+
 /* Host worker threads of a batch pass (verify_batch interpreter shards, tuple / Taproot front
  * ends, host-verified rounds).  0 restores the default: BCC_HOST_THREADS, else the CPUs of the
  * affinity mask, or the cgroup CPU quota when that is smaller, at most 64.  Results never
@@ -418,6 +427,21 @@ typedef struct bcc_batch_stats {
 } bcc_batch_stats;
 /* Statistics of the calling thread's last bitcoinconsensus_verify_batch / verify call. */
 void bcc_last_batch_stats(bcc_batch_stats* out);
+
+/* The deferred signature checks of a call by the way their sighash was computed: legacy
+ * SIGHASH_ALL from the tx template, other legacy hash types from the raw tx
+ * (bcc_set_device_hashtypes), BIP143 from the raw tx (SIGHASH_SINGLE counted apart; only with
+ * bcc_set_device_hashtypes), a host-serialized preimage per check (legacy non-ALL types and BIP143
+ * SIGHASH_SINGLE without bcc_set_device_hashtypes), legacy SIGHASH_SINGLE with n_in >= outputs
+ * (no job: the message is uint256 ONE), and the checks the host hashed itself
+ * (bcc_batch_stats.host_hashed). */
+typedef struct bcc_sighash_kinds {
+    size_t legacy_template, legacy_rawtx, bip143_rawtx, bip143_rawtx_single, host_preimage,
+        single_bug, host_hashed;
+} bcc_sighash_kinds;
+/* The counts of the calling thread's last bitcoinconsensus_verify_batch / verify call, summed over
+ * its rounds, or of its last bcc_debug_sighash call (include/bcc_bench.h), whichever was later. */
+void bcc_last_sighash_kinds(bcc_sighash_kinds* out);
 
 /* ---- host verification: the engine's own code on the CPU ------------------------------------
  * A device round (sighash jobs + ECDSA tuples) can be evaluated on the host with the engine's own

@@ -128,8 +128,19 @@ typedef struct bcc_sighash_check {
 /* Builds each check's device job exactly as the batch engine's deferring checker does and runs
  * only the sighash kernels on `device`; msg32_out receives the n message rows the ECDSA kernels
  * would read (the SHA-256d sighash as raw uint256 bytes; uint256 ONE for the SIGHASH_SINGLE bug).
- * Returns 0, -1 for a tx that does not parse / a bad index or sigversion, or a HIP error. */
+ * Returns 0, -1 for a tx that does not parse / a bad index or sigversion, or a HIP error.
+ * bcc_last_sighash_kinds (bcc_amd.h) then reports the job kinds the n checks became. */
 int bcc_debug_sighash(const bcc_sighash_check* checks, size_t n, uint8_t* msg32_out, int device);
+/* The same with the call's cost by part (tools/hashtype_bench.py): the host's job building, the
+ * staging of the pinned image, upload + kernels + the copy back of the digests (wall clock), the
+ * bytes uploaded, and the sighash kernels alone (event time of a second run of the stage over the
+ * inputs then resident in HBM).  timing may be NULL. */
+typedef struct bcc_sighash_timing {
+    double build_seconds, stage_seconds, run_seconds, kernel_seconds, total_seconds;
+    size_t upload_bytes;
+} bcc_sighash_timing;
+int bcc_debug_sighash_timed(const bcc_sighash_check* checks, size_t n, uint8_t* msg32_out, int device,
+                            bcc_sighash_timing* timing);
 
 /* ---- generator kernels (synthetic inputs; not on the verification path) -------------------- */
 int mi_gen_pubkeys(const uint8_t* d32, size_t n, uint8_t* x32, uint8_t* y32, uint8_t* ok,

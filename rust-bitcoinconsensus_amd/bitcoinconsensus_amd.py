@@ -204,20 +204,56 @@ def debug_sighash(checks, device=0):
     n = len(checks)
     if n == 0:
         return []
-    arr = (SighashCheck * n)()
-    keep = []
-    for i, (tx, code, nin, ht, amount, sv) in enumerate(checks):
-        tb, cb = ctypes.create_string_buffer(bytes(tx), max(1, len(tx))), \
-            ctypes.create_string_buffer(bytes(code), max(1, len(code)))
-        keep += [tb, cb]
-        ht = int(ht) & 0xffffffff
-        arr[i] = SighashCheck(ctypes.addressof(tb), len(tx), ctypes.addressof(cb), len(code), nin,
-                              ht - (1 << 32) if ht >= 1 << 31 else ht, amount, sv)
+    arr, keep = _sighash_checks(checks)
     out = ctypes.create_string_buffer(32 * n)
     rc = blib().bcc_debug_sighash(arr, n, out, device)
     if rc != 0:
         raise RuntimeError(f"bcc_debug_sighash failed: {rc}")
     return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+
+
+def _sighash_checks(checks, share_tx=False):
+    """(SighashCheck array, keep-alive buffers).  share_tx: adjacent checks whose tx is the same
+    bytes object share one buffer, so the job builder treats them as one transaction's checks."""
+    n = len(checks)
+    arr = (SighashCheck * n)()
+    keep = []
+    last, tb = None, None
+    for i, (tx, code, nin, ht, amount, sv) in enumerate(checks):
+        if not (share_tx and tx is last):
+            tb = ctypes.create_string_buffer(bytes(tx), max(1, len(tx)))
+            last = tx
+        cb = ctypes.create_string_buffer(bytes(code), max(1, len(code)))
+        keep += [tb, cb]
+        ht = int(ht) & 0xffffffff
+        arr[i] = SighashCheck(ctypes.addressof(tb), len(tx), ctypes.addressof(cb), len(code), nin,
+                              ht - (1 << 32) if ht >= 1 << 31 else ht, amount, sv)
+    return arr, keep
+
+
+class SighashTiming(ctypes.Structure):
+    """struct bcc_sighash_timing (include/bcc_bench.h)."""
+    _fields_ = [(f, ctypes.c_double) for f in ("build_seconds", "stage_seconds", "run_seconds",
+                                               "kernel_seconds", "total_seconds")] + [
+        ("upload_bytes", ctypes.c_size_t)]
+
+
+def debug_sighash_timed(checks, device=0):
+    """bcc_debug_sighash_timed: debug_sighash with the call's cost by part; adjacent checks with the
+    same tx object are one transaction's checks.  Returns (digests, timing dict)."""
+    n = len(checks)
+    arr, keep = _sighash_checks(checks, share_tx=True)
+    out = ctypes.create_string_buffer(32 * max(1, n))
+    t = SighashTiming()
+    L = blib()
+    L.bcc_debug_sighash_timed.argtypes = [ctypes.POINTER(SighashCheck), ctypes.c_size_t,
+                                          ctypes.c_char_p, ctypes.c_int,
+                                          ctypes.POINTER(SighashTiming)]
+    rc = L.bcc_debug_sighash_timed(arr, n, out, device, ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError(f"bcc_debug_sighash_timed failed: {rc}")
+    return ([out.raw[32 * i:32 * i + 32] for i in range(n)],
+            {f: getattr(t, f) for f, _ in SighashTiming._fields_})
 
 
 class TuplesetHost(ctypes.Structure):
@@ -452,6 +488,33 @@ def last_batch_stats():
     s = BatchStats()
     lib().bcc_last_batch_stats(ctypes.byref(s))
     return {k: getattr(s, k) for k, _ in BatchStats._fields_}
+
+
+class SighashKinds(ctypes.Structure):
+    """struct bcc_sighash_kinds (include/bcc_amd.h)."""
+    _fields_ = [(f, ctypes.c_size_t) for f in (
+        "legacy_template", "legacy_rawtx", "bip143_rawtx", "bip143_rawtx_single", "host_preimage",
+        "single_bug", "host_hashed")]
+
+
+def last_sighash_kinds():
+    """bcc_last_sighash_kinds: the deferred checks of the calling thread's last verify_batch /
+    verify (or debug_sighash) call by the way their sighash was computed."""
+    L = lib()
+    L.bcc_last_sighash_kinds.argtypes = [ctypes.POINTER(SighashKinds)]
+    L.bcc_last_sighash_kinds.restype = None
+    k = SighashKinds()
+    L.bcc_last_sighash_kinds(ctypes.byref(k))
+    return {f: getattr(k, f) for f, _ in SighashKinds._fields_}
+
+
+def set_device_hashtypes(on):
+    """bcc_set_device_hashtypes: legacy NONE / SINGLE / ANYONECANPAY and BIP143 SIGHASH_SINGLE
+    checks become device jobs built from the raw transaction instead of host-serialized preimages
+    (default off).  Results never depend on it."""
+    L = lib()
+    L.bcc_set_device_hashtypes.argtypes = [ctypes.c_int]
+    L.bcc_set_device_hashtypes(1 if on else 0)
 
 
 def debug_fail_device_rounds(rounds):

@@ -10,10 +10,13 @@
 // The staged device batch is exactly what bitcoinconsensus_verify_batch hands the GPU for these
 // inputs: the engine's own first-round interpreter pass (build_first_round) builds it.
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "pipeline.h"
 #include "bcc_amd.h"
@@ -771,8 +774,19 @@ extern "C" bcc_workload* bcc_workload_block(const uint32_t* tx_nin, const uint32
 // (K3'), host-serialized legacy preimages (K3), the SIGHASH_SINGLE bug (row stays ONE), BIP143
 // raw-tx jobs (K_wtx + K_win) and BIP143 SIGHASH_SINGLE preimages (K1 + K2 + K3).
 int bcc_debug_sighash(const bcc_sighash_check* checks, size_t n, uint8_t* msg32_out, int device) {
+    return bcc_debug_sighash_timed(checks, n, msg32_out, device, nullptr);
+}
+
+int bcc_debug_sighash_timed(const bcc_sighash_check* checks, size_t n, uint8_t* msg32_out, int device,
+                            bcc_sighash_timing* timing) {
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) {
+        return std::chrono::duration<double>(b - a).count();
+    };
+    if (timing) *timing = bcc_sighash_timing{};
     if (n == 0) return 0;
     if (!checks || !msg32_out) return -1;
+    const auto t0 = clk::now();
     std::vector<bcc::host::SighashCheck> c(n);
     for (size_t i = 0; i < n; i++)
         c[i] = bcc::host::SighashCheck{checks[i].tx,       checks[i].tx_len,
@@ -782,9 +796,39 @@ int bcc_debug_sighash(const bcc_sighash_check* checks, size_t n, uint8_t* msg32_
     bcc::SighashJobs jobs;
     bcc::TupleRows rows;
     if (bcc::host::build_sighash_checks(c.data(), n, jobs, rows) != n) return -1;
-    bcc::DeviceBatch batch(device);
-    int e = batch.stage(jobs, rows);
-    if (!e) e = batch.run_sighash(nullptr);
-    if (!e) e = batch.fetch_msgs(msg32_out);
+    const auto t1 = clk::now();
+    hipStream_t st = nullptr;  // (outlive the batch, whose last run they carry)
+    hipEvent_t ea = nullptr, eb = nullptr;
+    int e;
+    {
+        bcc::DeviceBatch batch(device);
+        e = batch.stage(jobs, rows);
+        const auto t2 = clk::now();
+        if (!e) e = batch.run_sighash(nullptr);
+        if (!e) e = batch.fetch_msgs(msg32_out);
+        const auto t3 = clk::now();
+        if (timing && !e) {
+            timing->build_seconds = secs(t0, t1);
+            timing->stage_seconds = secs(t1, t2);
+            timing->run_seconds = secs(t2, t3);
+            timing->total_seconds = secs(t0, t3);
+            timing->upload_bytes = batch.upload_bytes();
+            // the kernels alone: a second run of the stage over the inputs now resident in HBM
+            // (every kernel of it rewrites what its first run wrote), between two events
+            float ms = 0;
+            e = (int)hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+            if (!e) e = (int)hipEventCreate(&ea);
+            if (!e) e = (int)hipEventCreate(&eb);
+            if (!e) e = (int)hipEventRecord(ea, st);
+            if (!e) e = batch.run_sighash(st);
+            if (!e) e = (int)hipEventRecord(eb, st);
+            if (!e) e = (int)hipEventSynchronize(eb);
+            if (!e) e = (int)hipEventElapsedTime(&ms, ea, eb);
+            timing->kernel_seconds = ms * 1e-3;
+        }
+    }
+    if (ea) (void)hipEventDestroy(ea);
+    if (eb) (void)hipEventDestroy(eb);
+    if (st) (void)hipStreamDestroy(st);
     return e;
 }

@@ -55,6 +55,7 @@ int current_device() {
 namespace {
 
 thread_local bcc_batch_stats t_stats;
+thread_local bcc_sighash_kinds t_kinds;  // bcc_last_sighash_kinds
 
 // Fault injection (tests): the next N device rounds of any thread fail as if the HIP runtime had
 // returned g_fail_code (bcc_debug_fail_device_rounds[_code], or BCC_FAULT_INJECT at load time).
@@ -83,6 +84,8 @@ struct TxEntry {
     int64_t tpl = -1;               // legacy template offset in the current round (-1: none)
     uint32_t tpl_len = 0;
     int32_t wtx = -1;               // WtxRec index in the current round (-1: none)
+    uint32_t wtx_skip = 0;          // ... bytes of tx_to its upload leaves out after the version
+                                    // (2: the segwit marker and flag), for offsets into it
     int64_t htpl = -1;              // host-kept legacy template offset (HostJobs::tpl), -1: none
     int32_t hdig = -1;              // host-computed BIP143 per-tx digests (HostJobs::dig), -1: none
     int64_t etpl = -1;              // legacy template offset in the shard's early jobs, -1: none
@@ -158,6 +161,15 @@ std::atomic<uint32_t> g_host_bip143_blocks{[] {
 std::atomic<bool> g_device_key_hash{[] {
     const char* e = getenv("BCC_DEVICE_KEY_HASH");
     return !(e && atoi(e) == 0);
+}()};
+
+// Device jobs for the remaining ECDSA-era hash types (bcc_set_device_hashtypes /
+// BCC_DEVICE_HASHTYPES, default 0): legacy NONE / SINGLE / ANYONECANPAY checks become LinJobs and
+// BIP143 SIGHASH_SINGLE checks WinJobs, both assembled on the device from the tx uploaded once per
+// round, instead of one host-serialized preimage per check.  Results never depend on it.
+std::atomic<bool> g_device_hashtypes{[] {
+    const char* e = getenv("BCC_DEVICE_HASHTYPES");
+    return e && atoi(e) != 0;
 }()};
 
 struct Item {
@@ -354,6 +366,17 @@ void early_extract_item(Item& it, EarlyShard& es) {
     }
 }
 
+// One round's jobs by kind, added to the calling thread's counts (bcc_last_sighash_kinds).
+void count_kinds(const SighashJobs& j, size_t host_hashed) {
+    t_kinds.legacy_template += j.tjobs.size();
+    t_kinds.legacy_rawtx += j.ljobs.size();
+    t_kinds.bip143_rawtx += j.wjobs.size() - j.n_win_single;
+    t_kinds.bip143_rawtx_single += j.n_win_single;
+    t_kinds.host_preimage += j.pre_off.size();
+    t_kinds.single_bug += j.n_single_bug;
+    t_kinds.host_hashed += host_hashed;
+}
+
 struct Pending {
     uint32_t item;
     uint32_t slot;  // index of the check in the item's cache
@@ -450,6 +473,30 @@ bool add_sighash_job(SighashJobs& jobs, TxEntry& te, const bcc_batch_item& in, c
         rows->pad_msg(row + 1);
         return &rows->msg[32 * (size_t)row];
     };
+    const bool dev_ht = g_device_hashtypes.load(std::memory_order_relaxed);
+    // the tx among the round's raw txs (WtxRec), uploaded on first use
+    auto place_wtx = [&](bool table_only) {
+        if (te.wtx >= 0) {
+            if (!table_only) jobs.wtx[te.wtx].n_in &= ~WTX_TABLE_ONLY;
+            return;
+        }
+        const uint8_t* raw = in.tx_to;
+        const size_t len = in.tx_to_len;
+        if (tx.has_witness() && !tx.vout.empty() && len > 10) {
+            // upload the tx without marker, flag and witnesses (BIP144 layout: the
+            // inputs start at byte 6, the outputs end where the witnesses begin)
+            const Span& last = tx.vout.back().ser;
+            const size_t mid = (size_t)(last.p + last.n - (raw + 6));
+            te.wtx = (int32_t)jobs.add_wtx3(raw, 4, raw + 6, mid, raw + len - 4, 4,
+                                            tx.vin.size());
+            te.wtx_skip = 2;
+        } else {
+            te.wtx = (int32_t)jobs.add_wtx(raw, len, tx.vin.size());
+            te.wtx_skip = 0;
+        }
+        if (table_only) jobs.wtx[te.wtx].n_in |= WTX_TABLE_ONLY;
+        touched.push_back(&te);
+    };
     if (sv == SIGVERSION_BASE && legacy_all_type(hashtype)) {
         // device-assembled from the tx template (pipeline.h TplJob), or a host job.  A long
         // template carries its midstates (TPL_MID): a job then hashes only the blocks from its
@@ -494,6 +541,50 @@ bool add_sighash_job(SighashJobs& jobs, TxEntry& te, const bcc_batch_item& in, c
             flagged = early;
             jobs.tjobs.push_back(tj);
         }
+    } else if (sv == SIGVERSION_BASE && (hashtype & 0x1f) == 3 && nin >= tx.vout.size()) {
+        jobs.n_single_bug++;  // SIGHASH_SINGLE bug, msg stays ONE
+    } else if (sv == SIGVERSION_BASE && dev_ht) {
+        // assembled on the device from the raw tx bytes (pipeline.h LinJob); the lane hashes the
+        // whole preimage, so a chain above host->chain_blocks goes to the host as it did
+        const bool acp = (hashtype & 0x80) != 0;
+        const int base = hashtype & 0x1f;
+        build_script_code_field(code, scratch);
+        // the output bytes the preimage keeps, as a range of tx_to: the output count follows the
+        // last input's nSequence, the outputs end where the last one does
+        const uint8_t* oc = tx.vin.back().script_sig.end() + 4;
+        const uint8_t *o0 = oc, *o1 = tx.vout.empty() ? oc + 1 : tx.vout.back().ser.end();
+        size_t outsec = (size_t)(o1 - o0);
+        if (base == 2) {
+            o1 = o0;
+            outsec = 1;
+        } else if (base == 3) {
+            o0 = tx.vout[nin].ser.p;
+            o1 = tx.vout[nin].ser.end();
+            outsec = (nin + 1 < 253 ? 1 : 3) + 9 * (size_t)nin + (size_t)(o1 - o0);
+        }
+        const size_t nins = acp ? 1 : tx.vin.size();
+        const size_t plen = 4 + (nins < 253 ? 1 : nins <= 0xFFFF ? 3 : 5) + 41 * (nins - 1) + 40 +
+                            scratch.size() + outsec + 8;
+        const uint64_t nb = sha_padded_len(plen) / 64;
+        if (hb && nb > hb && host->take(nb)) {
+            build_legacy_preimage(tx, nin, code, hashtype, scratch);
+            msg_row();
+            host->pre.insert(host->pre.end(), scratch.begin(), scratch.end());
+            host->pre_off.push_back(host->pre.size());
+            host->pre_row.push_back(row);
+        } else {
+            place_wtx(true);
+            LinJob lj{};
+            lj.tx = (uint32_t)te.wtx;
+            lj.nin = nin;
+            lj.code_off = jobs.add_code(scratch.data(), scratch.size());
+            lj.code_len = (uint32_t)scratch.size();
+            lj.hashtype = (uint32_t)hashtype;
+            lj.row = row;
+            lj.out_off = (uint32_t)(o0 - in.tx_to) - te.wtx_skip;
+            lj.out_len = (uint32_t)(o1 - o0);
+            jobs.ljobs.push_back(lj);
+        }
     } else if (sv == SIGVERSION_BASE) {
         if (build_legacy_preimage(tx, nin, code, hashtype, scratch)) {
             const uint64_t nb = sha_padded_len(scratch.size()) / 64;
@@ -506,29 +597,16 @@ bool add_sighash_job(SighashJobs& jobs, TxEntry& te, const bcc_batch_item& in, c
                 jobs.add_pre(scratch.data(), scratch.size(), row);
             }
         }
-        // else: SIGHASH_SINGLE bug, msg stays ONE
-    } else if (hb143 && (te.hdig >= 0 || (te.wtx < 0 && bip143_tx_chain_blocks(tx) > hb143))) {
+    } else if (hb143 && (te.hdig >= 0 ||
+                         ((te.wtx < 0 || (jobs.wtx[te.wtx].n_in & WTX_TABLE_ONLY)) &&
+                          bip143_tx_chain_blocks(tx) > hb143))) {
         // a long BIP143 tx: every check of it on the host, at once
         host_bip143_sighash(*host, te, nin, code, hashtype, in.amount, scratch, bip143, touched,
                             msg_row());
-    } else if ((hashtype & 0x1f) != 3) {
+    } else if ((hashtype & 0x1f) != 3 || dev_ht) {
         // BIP143 assembled on the device from the raw tx bytes (pipeline.h WinJob): the
         // host appends the tx once per round and a record per check
-        if (te.wtx < 0) {
-            const uint8_t* raw = in.tx_to;
-            const size_t len = in.tx_to_len;
-            if (tx.has_witness() && !tx.vout.empty() && len > 10) {
-                // upload the tx without marker, flag and witnesses (BIP144 layout: the
-                // inputs start at byte 6, the outputs end where the witnesses begin)
-                const Span& last = tx.vout.back().ser;
-                const size_t mid = (size_t)(last.p + last.n - (raw + 6));
-                te.wtx = (int32_t)jobs.add_wtx3(raw, 4, raw + 6, mid, raw + len - 4, 4,
-                                                tx.vin.size());
-            } else {
-                te.wtx = (int32_t)jobs.add_wtx(raw, len, tx.vin.size());
-            }
-            touched.push_back(&te);
-        }
+        place_wtx(false);
         WinJob wj{};
         wj.tx = (uint32_t)te.wtx;
         wj.nin = nin;
@@ -538,6 +616,17 @@ bool add_sighash_job(SighashJobs& jobs, TxEntry& te, const bcc_batch_item& in, c
         wj.row = row;
         wj.amount_lo = (uint32_t)(uint64_t)in.amount;
         wj.amount_hi = (uint32_t)((uint64_t)in.amount >> 32);
+        if ((hashtype & 0x1f) == 3) {  // SIGHASH_SINGLE: output nin's range behind the code field
+            uint32_t tr[2] = {0, 0};
+            if (nin < tx.vout.size()) {
+                const Span& o = tx.vout[nin].ser;
+                tr[0] = (uint32_t)(o.p - in.tx_to) - te.wtx_skip;
+                tr[1] = (uint32_t)o.n;
+            }
+            const uint8_t* tb = reinterpret_cast<const uint8_t*>(tr);
+            jobs.code.insert(jobs.code.end(), tb, tb + 8);
+            jobs.n_win_single++;
+        }
         jobs.wjobs.push_back(wj);
     } else {  // SIGHASH_SINGLE: host preimage, single-output aux message
         Bip143Job& job = bip143;
@@ -1438,6 +1527,7 @@ void chunk_interpret_finish(ChunkRun& c, const std::vector<char>& ran, const std
                              c.rds[t].jobs.wjobs.size();
         t_stats.aux_messages += c.rds[t].jobs.aux_off.size() + 3 * c.rds[t].jobs.wtx.size();
         t_stats.host_hashed += c.rds[t].host.pending() + c.rds[t].host.inline_rows;
+        count_kinds(c.rds[t].jobs, c.rds[t].host.pending() + c.rds[t].host.inline_rows);
     }
     t_stats.rounds++;
     t_stats.tuples += npend;
@@ -1855,6 +1945,7 @@ constexpr unsigned PIPELINE_STAGE_THREADS = 4;
 long run_batch(const bcc_batch_item* items, size_t n, unsigned flags, int* ret_out,
                bitcoinconsensus_error* err_out) {
     t_stats = bcc_batch_stats{};
+    t_kinds = bcc_sighash_kinds{};
     t_stats.items = n;
     double gpu_s = 0;
     auto t0 = clk::now();
@@ -1983,17 +2074,23 @@ size_t build_sighash_checks(const SighashCheck* checks, size_t n, SighashJobs& j
     const uint8_t zero[32] = {0};
     uint8_t one[32] = {0};
     one[0] = 1;
+    size_t cur = 0;  // adjacent checks with the same tx buffer share its entry, as a batch's items do
     for (size_t i = 0; i < n; i++) {
         const SighashCheck& c = checks[i];
-        if (!c.tx || !parse_tx(c.tx, c.tx_len, txs[i].tx) || c.nin >= txs[i].tx.vin.size())
-            return i;
+        if (i == 0 || c.tx != checks[i - 1].tx || c.tx_len != checks[i - 1].tx_len) {
+            cur = i;
+            if (!c.tx || !parse_tx(c.tx, c.tx_len, txs[cur].tx)) return i;
+        }
+        if (c.nin >= txs[cur].tx.vin.size()) return i;
         if (c.sigversion != SIGVERSION_BASE && c.sigversion != SIGVERSION_WITNESS_V0) return i;
         bcc_batch_item in{nullptr, 0, c.amount, c.tx, (unsigned)c.tx_len, c.nin};
         const Bytes code(c.code, c.code + c.code_len);
         const uint32_t row = rows.add(0x02, zero, zero, zero, zero, one);
-        add_sighash_job(jobs, txs[i], in, code, (SigVersion)c.sigversion, c.hashtype, row, scratch,
+        add_sighash_job(jobs, txs[cur], in, code, (SigVersion)c.sigversion, c.hashtype, row, scratch,
                         bip143, touched);
     }
+    t_kinds = bcc_sighash_kinds{};
+    count_kinds(jobs, 0);
     return n;
 }
 
@@ -2046,6 +2143,14 @@ void append_round(SighashJobs& dst, TupleRows& drows, const SighashJobs& src,
         w.row += row0;
         dst.wjobs.push_back(w);
     }
+    for (LinJob l : src.ljobs) {
+        l.tx += wtx0;
+        l.code_off += code0;
+        l.row += row0;
+        dst.ljobs.push_back(l);
+    }
+    dst.n_single_bug += src.n_single_bug;
+    dst.n_win_single += src.n_win_single;
 }
 
 }  // namespace host
@@ -2128,6 +2233,15 @@ void bcc_debug_fail_device_rounds_code(int rounds, int hip_error) {
 int bcc_set_device_key_hash(int on) {
     bcc::host::g_device_key_hash.store(on != 0, std::memory_order_relaxed);
     return 0;
+}
+
+int bcc_set_device_hashtypes(int on) {
+    bcc::host::g_device_hashtypes.store(on != 0, std::memory_order_relaxed);
+    return 0;
+}
+
+void bcc_last_sighash_kinds(bcc_sighash_kinds* out) {
+    if (out) *out = t_kinds;
 }
 
 int bcc_set_host_chain_blocks(unsigned blocks) {

@@ -122,22 +122,66 @@ void host_sighash(const SighashJobs& j, uint8_t* msg) {
         }
     }
     for (const TplJob& t : j.tjobs) tpl_job_sighash(j.tpl.data(), j.code.data(), t, msg + 32 * (size_t)t.row);
-    if (!j.wjobs.empty()) {
-        // BIP143 from the raw tx bytes: parse each tx once, its three aux digests on first use
+    if (!j.wjobs.empty() || !j.ljobs.empty()) {
+        // from the raw tx bytes: parse each tx once; BIP143: its three aux digests on first use
         std::vector<Tx> txs(j.wtx.size());
-        std::vector<char> parsed(j.wtx.size(), 0);
+        std::vector<char> parsed(j.wtx.size(), 0);  // 1: parsed, 2: and its digests computed
         std::vector<uint8_t> digests(96 * j.wtx.size());
         Bip143Job job;
         std::vector<uint8_t> aux;
+        // legacy NONE / SINGLE / ANYONECANPAY (LinJob), as K_lin streams it: the inputs from the
+        // parsed tx, the code field and the output range as the job record names them
+        for (const LinJob& l : j.ljobs) {
+            const WtxRec& r = j.wtx[l.tx];
+            if (!parsed[l.tx]) {
+                if (!parse_tx(&j.txraw[r.tx_off], r.tx_len, txs[l.tx])) continue;  // row keeps ONE
+                parsed[l.tx] = 1;
+            }
+            const Tx& tx = txs[l.tx];
+            if (l.nin >= tx.vin.size() || l.out_off > r.tx_len || l.out_len > r.tx_len - l.out_off)
+                continue;
+            const bool acp = (l.hashtype & 0x80) != 0;
+            const uint32_t base = l.hashtype & 0x1f;
+            const uint8_t* t = &j.txraw[r.tx_off];
+            auto le = [&](uint64_t v, int k) {
+                for (int i = 0; i < k; i++) aux.push_back((uint8_t)(v >> (8 * i)));
+            };
+            aux.clear();
+            aux.insert(aux.end(), t, t + 4);
+            put_compact_size(aux, acp ? 1 : tx.vin.size());
+            for (size_t k = acp ? l.nin : 0; k < (acp ? l.nin + 1 : tx.vin.size()); k++) {
+                const TxIn& in = tx.vin[k];
+                aux.insert(aux.end(), in.prevout, in.prevout + 36);
+                if (k == l.nin) aux.insert(aux.end(), &j.code[l.code_off], &j.code[l.code_off] + l.code_len);
+                else aux.push_back(0);
+                le(k != l.nin && (base == 2 || base == 3) ? 0 : in.sequence, 4);
+            }
+            if (base == 2) {
+                aux.push_back(0);
+            } else {
+                if (base == 3) {
+                    put_compact_size(aux, (uint64_t)l.nin + 1);
+                    for (uint32_t k = 0; k < l.nin; k++) {
+                        le(~(uint64_t)0, 8);
+                        aux.push_back(0);
+                    }
+                }
+                aux.insert(aux.end(), t + l.out_off, t + l.out_off + l.out_len);
+            }
+            aux.insert(aux.end(), t + r.tx_len - 4, t + r.tx_len);
+            le(l.hashtype, 4);
+            sha256d(aux.data(), aux.size(), msg + 32 * (size_t)l.row);
+        }
         for (const WinJob& w : j.wjobs) {
             const WtxRec& r = j.wtx[w.tx];
-            if (!parsed[w.tx]) {
-                if (!parse_tx(&j.txraw[r.tx_off], r.tx_len, txs[w.tx])) continue;  // row keeps ONE
+            if (parsed[w.tx] != 2) {
+                if (!parsed[w.tx] && !parse_tx(&j.txraw[r.tx_off], r.tx_len, txs[w.tx]))
+                    continue;  // row keeps ONE
                 for (int k = 0; k < 3; k++) {
                     build_aux_message(txs[w.tx], (AuxKind)k, aux);
                     sha256d(aux.data(), aux.size(), &digests[96 * w.tx + 32 * k]);
                 }
-                parsed[w.tx] = 1;
+                parsed[w.tx] = 2;
             }
             const Tx& tx = txs[w.tx];
             if (w.nin >= tx.vin.size()) continue;
@@ -148,6 +192,16 @@ void host_sighash(const SighashJobs& j, uint8_t* msg) {
             build_bip143_preimage(tx, w.nin, code, (int)w.hashtype, amount, job);
             for (int k = 0; k < 3; k++)
                 if (job.need[k]) memcpy(&job.preimage[job.off[k]], &digests[96 * w.tx + 32 * k], 32);
+            if ((w.hashtype & 0x1f) == 3) {  // hashOutputs: output nin alone (its range follows
+                                             // the code field), zero when nin >= outputs
+                uint32_t tr[2];
+                memcpy(tr, &j.code[win_single_trailer(w)], 8);
+                uint8_t* slot = &job.preimage[job.off[AUX_OUTPUTS]];
+                if (tr[1] && tr[0] <= r.tx_len && tr[1] <= r.tx_len - tr[0])
+                    sha256d(&j.txraw[r.tx_off + tr[0]], tr[1], slot);
+                else
+                    memset(slot, 0, 32);
+            }
             sha256d(job.preimage.data(), job.preimage.size(), msg + 32 * (size_t)w.row);
         }
     }

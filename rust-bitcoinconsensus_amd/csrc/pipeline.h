@@ -3,6 +3,7 @@
 //   K2 patch(aux digests -> preimages)
 //   K3 sha256d(preimages)           legacy + BIP143 sighashes, written as the tuple msg rows
 //   K3' sha256d(template jobs)      legacy SIGHASH_ALL sighashes assembled from per-tx templates
+//   K_lin sha256d(raw-tx jobs)      other legacy hash types assembled from the raw tx (LinJob)
 //   K4 ecdsa_verify(tuples)         csrc/ecdsa_verify.hip
 // All four launch back-to-back on one stream with inputs resident in HBM.
 #pragma once
@@ -137,18 +138,45 @@ struct WtxRec {
     uint32_t tx_off;   // byte offset of the raw tx in the txraw blob (4-aligned)
     uint32_t tx_len;
     uint32_t in_base;  // first entry of this tx's inputs in the device input table
-    uint32_t n_in;     // vin.size() as the host parsed it (table capacity)
+    uint32_t n_in;     // vin.size() as the host parsed it (table capacity) | WTX_TABLE_ONLY
 };
+// A tx that only legacy jobs (LinJob) read: K_wtx writes its input table and hashes nothing (the
+// three BIP143 digests have no reader).  The first WinJob of the tx clears the flag.
+constexpr uint32_t WTX_TABLE_ONLY = 0x80000000u;
+BCC_PL_HD inline uint32_t wtx_n_in(const WtxRec& r) { return r.n_in & ~WTX_TABLE_ONLY; }
 struct WinJob {
     uint32_t tx;        // WtxRec index
     uint32_t nin;
     uint32_t code_off;  // compactsize || scriptCode in the code blob (4-aligned)
     uint32_t code_len;
-    uint32_t hashtype;  // not SIGHASH_SINGLE (those keep the host preimage path)
+    uint32_t hashtype;  // SIGHASH_SINGLE only with bcc_set_device_hashtypes (else the host
+                        // preimage path): two dwords then follow the code field (4-aligned) in the
+                        // code blob, output nin's offset in the uploaded tx and its length (0:
+                        // nin >= outputs, hashOutputs is zero)
     uint32_t row;       // tuple row whose msg receives the sighash
     uint32_t amount_lo, amount_hi;
 };
 static_assert(sizeof(WinJob) == 32, "WinJob: two 16-byte loads");
+BCC_PL_HD inline uint32_t win_single_trailer(const WinJob& j) {  // code blob offset of the two dwords
+    return j.code_off + ((j.code_len + 3) & ~3u);
+}
+
+// Legacy NONE / SINGLE / ANYONECANPAY jobs built on the device from the raw transaction bytes
+// (bcc_set_device_hashtypes): K_lin streams CTransactionSignatureSerializer's preimage
+// (interpreter.cpp:1273-1364) from the uploaded tx (the WinJobs' WtxRec and input table), the code
+// field and this record.  The host has parsed the tx, so the output bytes the preimage keeps travel
+// as a range of the uploaded tx: SINGLE: output nin alone; NONE: nothing; otherwise the whole
+// output section, count included.
+struct LinJob {
+    uint32_t tx;        // WtxRec index
+    uint32_t nin;
+    uint32_t code_off;  // compactsize || scriptCode without OP_CODESEPARATORs (4-aligned)
+    uint32_t code_len;
+    uint32_t hashtype;
+    uint32_t row;       // tuple row whose msg receives the sighash
+    uint32_t out_off, out_len;
+};
+static_assert(sizeof(LinJob) == 32, "LinJob: two 16-byte loads");
 
 struct SighashJobs {
     pinned_bytes aux, pre;                          // padded messages, back to back
@@ -161,7 +189,11 @@ struct SighashJobs {
     pinned_bytes txraw;                             // raw txs of the WinJobs (4-aligned)
     std::vector<WtxRec> wtx;
     std::vector<WinJob> wjobs;
+    std::vector<LinJob> ljobs;
     uint32_t win_entries = 0;                       // sum of WtxRec::n_in
+    // job-kind counts the records do not show (bcc_last_sighash_kinds): SIGHASH_SINGLE-bug checks
+    // (no job, the row keeps ONE) and the SIGHASH_SINGLE jobs among wjobs
+    uint32_t n_single_bug = 0, n_win_single = 0;
     uint32_t add_wtx(const uint8_t* tx, size_t n, size_t n_in) {
         WtxRec r;
         r.tx_off = (uint32_t)txraw.size();
@@ -237,6 +269,7 @@ struct SighashJobs {
         pre_off.clear(); pre_nblk.clear(); pre_row.clear(); patches.clear();
         tpl.clear(); code.clear(); tjobs.clear();
         txraw.clear(); wtx.clear(); wjobs.clear(); win_entries = 0;
+        ljobs.clear(); n_single_bug = n_win_single = 0;
     }
 };
 
@@ -585,12 +618,18 @@ public:
     int fetch_msgs(uint8_t* out);                // synchronous D2H (tests)
     size_t n_tuples() const { return n_rows_; }
     size_t n_key_hashes() const { return n_hash_; }  // TupleRows::hrow conditions staged
-    size_t n_pre() const { return n_pre_ + n_tjob_ + n_wjob_; }  // sighash messages (all kinds)
+    size_t n_pre() const { return n_pre_ + n_tjob_ + n_wjob_ + n_ljob_; }  // sighash messages (all kinds)
     size_t n_wtx() const { return n_wtx_; }
     // Algorithmic bytes of one run of the sighash stage: padded messages + digests of the host-built
     // jobs, and raw tx bytes + job records + scriptCode fields + per-tx hashes + sighashes of the
     // device-built BIP143 jobs.
     size_t sighash_bytes() const { return sighash_bytes_; }
+    // Bytes the staged round sends to the device (tuple rows and sighash inputs; until the next stage).
+    size_t upload_bytes() const {
+        size_t s = 0;
+        for (const UpCopy& c : up_copies_) s += c.len;
+        return s;
+    }
     size_t n_aux() const { return n_aux_; }
     size_t pre_blocks() const { return pre_blocks_ + tjob_blocks_; }
     size_t aux_blocks() const { return aux_blocks_; }
@@ -625,7 +664,7 @@ private:
     void* ev_pre_ = nullptr;           // hipEvent_t: every pre-upload issued so far is done
     bool gather_pending_ = false;      // the next run gathers the pre-uploaded rows (upload_on)
     std::vector<size_t> gather_row0_;  // the shards' first rows in the arena (P + 1)
-    int launch_after_front(struct ihipStream_t* st);  // K_win, K2, K3
+    int launch_after_front(struct ihipStream_t* st);  // K_win, K_lin, K2, K3
     int launch_key_hash(struct ihipStream_t* st);     // K_h160: key-hash conditions into the verdicts
     int run_stages(void* stream, const LateMsgFill* late);
     int put_late(struct ihipStream_t* st, const LateMsgFill* late);  // late rows -> d_m (K_late)
@@ -671,6 +710,8 @@ private:
     uint8_t *d_txraw_ = nullptr, *d_txd_ = nullptr, *d_zeros_ = nullptr;
     WtxRec* d_wtx_ = nullptr;
     WinJob* d_wjob_ = nullptr;
+    size_t n_ljob_ = 0;
+    LinJob* d_ljob_ = nullptr;
     uint32_t* d_intab_ = nullptr;
     size_t n_hash_ = 0;
     uint32_t* d_hrow_ = nullptr;

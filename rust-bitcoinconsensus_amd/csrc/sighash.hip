@@ -349,9 +349,9 @@ __device__ __forceinline__ void xs_put(XSha& h, const uint8_t* __restrict__ src,
     }
 }
 
-// SHA-256 padding + final compression(s), then the second SHA-256 of SHA-256d: big-endian
-// digest bytes to out (4-aligned).
-__device__ __forceinline__ void xs_final_d(XSha& h, uint8_t* __restrict__ out) {
+// SHA-256 padding + final compression(s), then the second SHA-256 of SHA-256d: the digest as
+// eight big-endian words.
+__device__ __forceinline__ void xs_final_dw(XSha& h, uint32_t e[8]) {
     const uint64_t bits = (uint64_t)h.total * 8;
     h.slot[h.fill++] = 0x80;
     if (h.fill > 56) {
@@ -364,13 +364,31 @@ __device__ __forceinline__ void xs_final_d(XSha& h, uint8_t* __restrict__ out) {
     for (int k = 0; k < 8; k++) h.slot[56 + k] = (uint8_t)(bits >> (8 * (7 - k)));
     xs_compress(h.slot);
     const uint32_t* st = reinterpret_cast<const uint32_t*>(h.slot + 64);
-    uint32_t d[8], e[8];
+    uint32_t d[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) d[k] = st[k];
     sha256_of_digest(e, d);
+}
+
+// ... as big-endian digest bytes to out (16-aligned).
+__device__ __forceinline__ void xs_final_d(XSha& h, uint8_t* __restrict__ out) {
+    uint32_t e[8];
+    xs_final_dw(h, e);
     uint4* o = reinterpret_cast<uint4*>(out);
     o[0] = make_uint4(bswap_u32(e[0]), bswap_u32(e[1]), bswap_u32(e[2]), bswap_u32(e[3]));
     o[1] = make_uint4(bswap_u32(e[4]), bswap_u32(e[5]), bswap_u32(e[6]), bswap_u32(e[7]));
+}
+
+// the first `n` (<= 4) little-endian bytes of v, from registers
+__device__ __forceinline__ void xs_put_le(XSha& h, uint32_t v, uint32_t n) {
+    h.total += n;
+    for (uint32_t k = 0; k < n; k++) {
+        h.slot[h.fill++] = (uint8_t)(v >> (8 * k));
+        if (h.fill == 64) {
+            xs_compress(h.slot);
+            h.fill = 0;
+        }
+    }
 }
 
 // The wire bytes of one tx seen through a 128-byte window in the lane's LDS slot: a refill
@@ -491,6 +509,8 @@ __device__ __forceinline__ void bip143_tx_lane(const uint8_t* __restrict__ txraw
                                                uint8_t* __restrict__ txd, uint8_t* win) {
     const uint32_t role = g / n, i = g - role * n;
     const WtxRec r = recs[i];
+    const bool table_only = (r.n_in & WTX_TABLE_ONLY) != 0;  // only legacy jobs read this tx
+    if (table_only && role) return;
     const uint8_t* t = txraw + r.tx_off;
     const uint32_t* t4 = reinterpret_cast<const uint32_t*>(t);
     XWin x;
@@ -502,7 +522,16 @@ __device__ __forceinline__ void bip143_tx_lane(const uint8_t* __restrict__ txraw
     uint32_t pos = 4;
     uint32_t nin = wire_cs(x, pos);
     if (nin == 0 && xw_byte(x, pos++) != 0) nin = wire_cs(x, pos);  // marker 0x00, flag (BIP144)
-    nin = min(nin, r.n_in);
+    nin = min(nin, wtx_n_in(r));
+    if (table_only) {  // the input table alone: no hashPrevouts
+        uint32_t* tab = intab + 2 * (size_t)r.in_base;
+        for (uint32_t k = 0; k < nin; k++) {
+            uint32_t sq;
+            tab[2 * k] = wire_input(x, pos, &sq);
+            tab[2 * k + 1] = sq;
+        }
+        return;
+    }
     uint8_t* d = txd + 96 * (size_t)i;
     uint32_t st[8];
     sha256_init_state(st);
@@ -618,11 +647,13 @@ __global__ __launch_bounds__(XS_WG) void sighash_front_kernel(
         sha256d_msg_lane(aux, aux_off, aux_nblk, g - nw - ntpl, auxd, nullptr);
 }
 
-// K_win: one lane per BIP143 check (not SIGHASH_SINGLE).  SignatureHash WITNESS_V0
+// K_win: one lane per BIP143 check.  SignatureHash WITNESS_V0
 // (interpreter.cpp:1581-1625): version || hashPrevouts || hashSequence || outpoint ||
 // scriptCode || amount || nSequence || hashOutputs || locktime || hashtype, with the hashes
 // zeroed per ANYONECANPAY / NONE, streamed from the tx bytes, the K_wtx digests and the job
-// record, SHA-256d into the tuple's msg row.
+// record, SHA-256d into the tuple's msg row.  SIGHASH_SINGLE: hashOutputs is the SHA-256d of output
+// nin alone, hashed here first in the same LDS slot from the range that follows the code field
+// (pipeline.h WinJob), or zero when nin >= outputs.
 __global__ __launch_bounds__(XS_WG) void bip143_in_kernel(const uint8_t* __restrict__ txraw,
                                                           const WtxRec* __restrict__ recs,
                                                           const WinJob* __restrict__ jobs,
@@ -641,18 +672,123 @@ __global__ __launch_bounds__(XS_WG) void bip143_in_kernel(const uint8_t* __restr
     const uint8_t* d = txd + 96 * (size_t)j.tx;
     const uint32_t* tab = intab + 2 * ((size_t)r.in_base + j.nin);
     const bool acp = (j.hashtype & 0x80) != 0, none = (j.hashtype & 0x1f) == 2;
+    const bool single = (j.hashtype & 0x1f) == 3;
     XSha h;
+    uint32_t so[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // SINGLE: hashOutputs, little-endian dwords
+    if (single) {
+        const uint32_t* tr = reinterpret_cast<const uint32_t*>(code + win_single_trailer(j));
+        const uint32_t o0 = tr[0], ol = tr[1];
+        if (ol && o0 <= r.tx_len && ol <= r.tx_len - o0) {
+            xs_init(h, lds + threadIdx.x * XS_SLOT);
+            xs_put(h, t + o0, ol);
+            uint32_t e[8];
+            xs_final_dw(h, e);
+#pragma unroll
+            for (int k = 0; k < 8; k++) so[k] = bswap_u32(e[k]);
+        }
+    }
     xs_init(h, lds + threadIdx.x * XS_SLOT);
     xs_put(h, t, 4);
     xs_put(h, acp ? zeros : d, 32);
-    xs_put(h, acp || none ? zeros : d + 32, 32);
+    xs_put(h, acp || none || single ? zeros : d + 32, 32);
     xs_put(h, t + tab[0], 36);
     xs_put(h, code + j.code_off, j.code_len);
     xs_put(h, reinterpret_cast<const uint8_t*>(&jp->amount_lo), 8);
     xs_put(h, t + tab[1], 4);
-    xs_put(h, none ? zeros : d + 64, 32);
+    if (single) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) xs_put_le(h, so[k], 4);
+    } else {
+        xs_put(h, none ? zeros : d + 64, 32);
+    }
     xs_put(h, t + r.tx_len - 4, 4);
     xs_put(h, reinterpret_cast<const uint8_t*>(&jp->hashtype), 4);
+    xs_final_d(h, msg + 32 * (size_t)j.row);
+}
+
+// CompactSize of a count the host has parsed (below MAX_SIZE), from registers
+__device__ __forceinline__ void xs_put_cs(XSha& h, uint32_t v) {
+    if (v < 253) {
+        xs_put_le(h, v, 1);
+    } else if (v <= 0xFFFFu) {
+        xs_put_le(h, 253u | v << 8, 3);
+    } else {
+        xs_put_le(h, 254u, 1);
+        xs_put_le(h, v, 4);
+    }
+}
+
+// xs_put behind a dword-aligned fill: the (at most three) bytes up to the next dword boundary of
+// the block buffer go in from registers first, so that xs_put takes its dword path.  K_lin's 41-byte
+// input records leave the fill unaligned three times out of four, and a wave takes xs_put's
+// byte-by-byte path when any of its lanes does.
+__device__ __forceinline__ void xs_put_headed(XSha& h, const uint8_t* __restrict__ src, uint32_t n) {
+    const uint32_t head = (4u - (h.fill & 3u)) & 3u;
+    if (head && n > head) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(src);
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+        const uint32_t sh = (uint32_t)(a & 3);
+        const uint32_t lo = w[0], hi = sh + head > 4u ? w[1] : 0u;  // (only the dwords the bytes are in)
+        xs_put_le(h, __builtin_amdgcn_alignbyte(hi, lo, sh), head);
+        src += head;
+        n -= head;
+    }
+    xs_put(h, src, n);
+}
+
+// K_lin: one lane per legacy check whose hash type is not plain SIGHASH_ALL (pipeline.h LinJob).
+// CTransactionSignatureSerializer (interpreter.cpp:1273-1364): version || inputs (ANYONECANPAY:
+// the signing input alone; each outpoint || script || nSequence, the script being the code field
+// for the signing input and empty for the others, whose nSequence is zero under NONE / SINGLE) ||
+// outputs (NONE: none; SINGLE: nin null outputs, then output nin; else all) || locktime ||
+// hashtype, streamed from the uploaded tx through the input table K_wtx wrote, SHA-256d into the
+// tuple's msg row.  Like K_win a lane is one serial SHA chain in its own LDS slot.
+__global__ __launch_bounds__(XS_WG) void legacy_in_kernel(const uint8_t* __restrict__ txraw,
+                                                          const WtxRec* __restrict__ recs,
+                                                          const LinJob* __restrict__ jobs,
+                                                          uint32_t n, const uint32_t* __restrict__ intab,
+                                                          const uint8_t* __restrict__ code,
+                                                          uint8_t* __restrict__ msg) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[XS_WG * XS_SLOT];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const LinJob j = jobs[i];
+    const WtxRec r = recs[j.tx];
+    const uint8_t* t = txraw + r.tx_off;
+    const uint32_t* tab = intab + 2 * (size_t)r.in_base;
+    const uint32_t n_in = wtx_n_in(r);
+    const bool acp = (j.hashtype & 0x80) != 0, none = (j.hashtype & 0x1f) == 2;
+    const bool single = (j.hashtype & 0x1f) == 3;
+    const uint32_t k0 = acp ? j.nin : 0u, k1 = acp ? j.nin + 1 : n_in;
+    if (j.nin >= n_in || j.out_off > r.tx_len || j.out_len > r.tx_len - j.out_off) return;  // (never
+                                                                // built by the host: the row keeps ONE)
+    XSha h;
+    xs_init(h, lds + threadIdx.x * XS_SLOT);
+    xs_put(h, t, 4);
+    xs_put_cs(h, k1 - k0);
+    for (uint32_t k = k0; k < k1; k++) {
+        const bool own = k == j.nin;
+        xs_put_headed(h, t + tab[2 * k], 36);
+        if (own) xs_put_headed(h, code + j.code_off, j.code_len);
+        else xs_put_le(h, 0u, 1);
+        if (!own && (none || single)) xs_put_le(h, 0u, 4);
+        else xs_put(h, t + tab[2 * k + 1], 4);
+    }
+    if (none) {
+        xs_put_le(h, 0u, 1);
+    } else {
+        if (single) {  // CTxOut(): nValue -1, empty script
+            xs_put_cs(h, j.nin + 1);
+            for (uint32_t k = 0; k < j.nin; k++) {
+                xs_put_le(h, 0xFFFFFFFFu, 4);
+                xs_put_le(h, 0xFFFFFFFFu, 4);
+                xs_put_le(h, 0u, 1);
+            }
+        }
+        xs_put_headed(h, t + j.out_off, j.out_len);
+    }
+    xs_put(h, t + r.tx_len - 4, 4);
+    xs_put_le(h, j.hashtype, 4);
     xs_final_d(h, msg + 32 * (size_t)j.row);
 }
 
@@ -679,18 +815,6 @@ __device__ __forceinline__ void xs_final_s(XSha& h, uint8_t* __restrict__ out) {
     uint32_t* o = reinterpret_cast<uint32_t*>(out);
 #pragma unroll
     for (int k = 0; k < 8; k++) o[k] = bswap_u32(st[k]);
-}
-
-// the first `n` (<= 4) little-endian bytes of v, from registers
-__device__ __forceinline__ void xs_put_le(XSha& h, uint32_t v, uint32_t n) {
-    h.total += n;
-    for (uint32_t k = 0; k < n; k++) {
-        h.slot[h.fill++] = (uint8_t)(v >> (8 * k));
-        if (h.fill == 64) {
-            xs_compress(h.slot);
-            h.fill = 0;
-        }
-    }
 }
 
 // The serialized spent outputs (std::vector<CTxOut>: compactsize count, then value || script):
@@ -1152,7 +1276,7 @@ int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const
     n_der_ = 0;
     std::vector<size_t> row0(P + 1, 0), auxb0(P + 1, 0), preb0(P + 1, 0), auxi0(P + 1, 0),
         prei0(P + 1, 0), pat0(P + 1, 0), tpl0(P + 1, 0), code0(P + 1, 0), tj0(P + 1, 0),
-        raw0(P + 1, 0), wtx0(P + 1, 0), wj0(P + 1, 0), win0(P + 1, 0), h0(P + 1, 0);
+        raw0(P + 1, 0), wtx0(P + 1, 0), wj0(P + 1, 0), win0(P + 1, 0), h0(P + 1, 0), lj0(P + 1, 0);
     for (size_t p = 0; p < P; p++) {
         row0[p + 1] = row0[p] + Rw[p]->size();
         auxb0[p + 1] = auxb0[p] + J[p]->aux.size();
@@ -1166,6 +1290,7 @@ int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const
         raw0[p + 1] = raw0[p] + J[p]->txraw.size();
         wtx0[p + 1] = wtx0[p] + J[p]->wtx.size();
         wj0[p + 1] = wj0[p] + J[p]->wjobs.size();
+        lj0[p + 1] = lj0[p] + J[p]->ljobs.size();
         win0[p + 1] = win0[p] + J[p]->win_entries;
         h0[p + 1] = h0[p] + Rw[p]->hrow.size();
     }
@@ -1189,13 +1314,14 @@ int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const
 
     n_wtx_ = wtx0[P];
     n_wjob_ = wj0[P];
+    n_ljob_ = lj0[P];
     n_win_ = win0[P];
     n_hash_ = h0[P];
     const size_t R = n_rows_;
     // regions filled from the host image first (one copy), device-written ones after them
     // Y and M go up only when some part needs them (TupleRows::y_unused / msg_one)
     enum { TAG, X, RR, S, EMAP, MMAP, AUX, PRE, AUX_OFF, AUX_NBLK, PRE_OFF, PRE_NBLK, PRE_ROW, PATCH,
-           TPL, CODE, TJOB, TXRAW, WTX, WJOB, HROW, HPROG, ZEROS, UPLOADED, Y = UPLOADED, M, V, AUXD, INTAB, TXD,
+           TPL, CODE, TJOB, TXRAW, WTX, WJOB, LJOB, HROW, HPROG, ZEROS, UPLOADED, Y = UPLOADED, M, V, AUXD, INTAB, TXD,
            NB };
     bool need_y = false, need_m = false, need_e = false, need_mm = false;
     for (size_t p = 0; p < P; p++) {
@@ -1217,6 +1343,7 @@ int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const
     sizes[PATCH] = sizeof(PatchRec) * n_patch_;
     sizes[TPL] = tpl0[P]; sizes[CODE] = code0[P]; sizes[TJOB] = sizeof(TplJob) * n_tjob_;
     sizes[TXRAW] = raw0[P]; sizes[WTX] = sizeof(WtxRec) * n_wtx_; sizes[WJOB] = sizeof(WinJob) * n_wjob_;
+    sizes[LJOB] = sizeof(LinJob) * n_ljob_;
     sizes[HROW] = 4 * n_hash_; sizes[HPROG] = 20 * n_hash_;
     sizes[ZEROS] = 64;
     sizes[V] = R; sizes[AUXD] = 32 * n_aux_; sizes[INTAB] = 8 * n_win_; sizes[TXD] = 96 * n_wtx_;
@@ -1249,6 +1376,7 @@ int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const
     d_pre_row_ = (uint32_t*)(a + off[PRE_ROW]); d_patch_ = (PatchRec*)(a + off[PATCH]);
     d_tpl_ = a + off[TPL]; d_code_ = a + off[CODE]; d_tjob_ = (TplJob*)(a + off[TJOB]);
     d_txraw_ = a + off[TXRAW]; d_wtx_ = (WtxRec*)(a + off[WTX]); d_wjob_ = (WinJob*)(a + off[WJOB]);
+    d_ljob_ = (LinJob*)(a + off[LJOB]);
     d_hrow_ = (uint32_t*)(a + off[HROW]); d_hprog_ = a + off[HPROG];
     d_zeros_ = a + off[ZEROS]; d_intab_ = (uint32_t*)(a + off[INTAB]); d_txd_ = a + off[TXD];
     d_emap_ = need_e ? (uint32_t*)(a + off[EMAP]) : nullptr;
@@ -1334,7 +1462,7 @@ int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const
         WtxRec* wr = (WtxRec*)(h + off[WTX]) + wtx0[p];
         for (size_t k = 0; k < j.wtx.size(); k++) {
             WtxRec t = j.wtx[k];
-            wb += t.tx_len + 96;
+            wb += t.tx_len + ((t.n_in & WTX_TABLE_ONLY) ? 0 : 96);
             t.tx_off += (uint32_t)raw0[p];
             t.in_base += (uint32_t)win0[p];
             wr[k] = t;
@@ -1347,6 +1475,15 @@ int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const
             t.code_off += (uint32_t)code0[p];
             t.row += (uint32_t)r0;
             wj[k] = t;
+        }
+        LinJob* lj = (LinJob*)(h + off[LJOB]) + lj0[p];
+        for (size_t k = 0; k < j.ljobs.size(); k++) {
+            LinJob t = j.ljobs[k];
+            wb += t.code_len + sizeof(LinJob) + 32;
+            t.tx += (uint32_t)wtx0[p];
+            t.code_off += (uint32_t)code0[p];
+            t.row += (uint32_t)r0;
+            lj[k] = t;
         }
         uint32_t* hr = (uint32_t*)(h + off[HROW]) + h0[p];
         for (size_t k = 0; k < rw.hrow.size(); k++) hr[k] = rw.hrow[k] + (uint32_t)r0;
@@ -1449,7 +1586,7 @@ int DeviceBatch::stage_der(const DerTuples& t) {
     const uint64_t pb = t.pub_bytes(), sb = t.sig_bytes();
     n_rows_ = R;
     n_pre_ = n_aux_ = n_patch_ = pre_blocks_ = aux_blocks_ = n_tjob_ = tjob_blocks_ = 0;
-    n_wtx_ = n_wjob_ = n_win_ = n_hash_ = sighash_bytes_ = 0;
+    n_wtx_ = n_wjob_ = n_ljob_ = n_win_ = n_hash_ = sighash_bytes_ = 0;
     d_emap_ = nullptr;
     n_der_ = 0;
     enum { PUB, SIG, POFF, SOFF, M, UPLOADED, TAG = UPLOADED, X, Y, RR, S, V, NB };
@@ -1686,12 +1823,18 @@ int DeviceBatch::upload_on(hipStream_t rows_stream, hipStream_t rest_stream, int
     return 0;
 }
 
-// K_win, K2, K3: everything of the sighash stage after K_wtx / K1 / K3'.
+// K_win, K_lin, K2, K3: everything of the sighash stage after K_wtx / K1 / K3'.
 int DeviceBatch::launch_after_front(hipStream_t st) {
     if (n_wjob_) {  // K_win: BIP143 preimages assembled from the raw tx bytes and hashed
         hipLaunchKernelGGL(bip143_in_kernel, dim3((unsigned)((n_wjob_ + XS_WG - 1) / XS_WG)),
                            dim3(XS_WG), 0, st, d_txraw_, d_wtx_, d_wjob_, (uint32_t)n_wjob_,
                            d_intab_, d_txd_, d_code_, d_zeros_, d_m);
+        BCC_HIP_TRY(hipGetLastError());
+    }
+    if (n_ljob_) {  // K_lin: legacy NONE / SINGLE / ANYONECANPAY preimages from the raw tx bytes
+        hipLaunchKernelGGL(legacy_in_kernel, dim3((unsigned)((n_ljob_ + XS_WG - 1) / XS_WG)),
+                           dim3(XS_WG), 0, st, d_txraw_, d_wtx_, d_ljob_, (uint32_t)n_ljob_,
+                           d_intab_, d_code_, d_m);
         BCC_HIP_TRY(hipGetLastError());
     }
     if (n_patch_) {
@@ -1881,7 +2024,7 @@ int DeviceBatch::run(void* stream, const LateMsgFill* late) {
     BCC_HIP_TRY(hipSetDevice(dev_));
     hipStream_t st = (hipStream_t)pick(stream);
     if (!st) return (int)hipErrorOutOfMemory;
-    if (n_rows_ == 0 || n_aux_ + n_tjob_ + n_pre_ + n_wjob_ == 0) {
+    if (n_rows_ == 0 || n_aux_ + n_tjob_ + n_pre_ + n_wjob_ + n_ljob_ == 0) {
         if (int e = run_sighash(st)) return e;
         if (late)
             if (int e = put_late(st, late)) return e;
