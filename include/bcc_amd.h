@@ -37,7 +37,10 @@ int mi_ecdsa_verify_device(const uint8_t* d_tag, const uint8_t* d_x, const uint8
  * (secp256k1/src/modules/extrakeys/main_impl.h:21-39, modules/schnorrsig/main_impl.h:190-237),
  * as bound by Core's XOnlyPubKey::VerifySchnorr (depend/bitcoin/src/pubkey.cpp:176-182).
  * Row i: sig64 = r.x || s, msg32, xonly32 = the key's 32 serialized bytes (a key that does not
- * parse verifies false).  verdict[i] = 1 iff valid. */
+ * parse verifies false).  verdict[i] = 1 iff valid.  Synchronous on `device`; at most
+ * bcc_set_host_small_round() rows run on the host CPU and touch no device state, and a device
+ * round that fails is handled as "the Taproot side's failure handling" below describes.  Returns
+ * 0, or under BCC_DEVICE_FAILURE_ERROR the HIP error of a failed round. */
 int mi_schnorr_verify_tuples(const uint8_t* sig64, const uint8_t* msg32, const uint8_t* xonly32,
                              uint8_t* verdict, size_t n, int device);
 /* Same with device-resident rows, launched on `stream`.  Asynchronous. */
@@ -84,8 +87,11 @@ typedef struct bcc_taproot_check {
  * n_in >= inputs, or no witness-bearing input spends a 34-byte OP_1 script (the tx data would not
  * be BIP341-ready); serror_out[i] = 1 (SCRIPT_ERR_UNKNOWN_ERROR) then.  sighash_out (optional,
  * 32 bytes per item): the signature hash where one was computed, else zeros.  Synchronous on
- * `device`, or for device = -1 spread over the bcc_set_devices() GPUs.  Returns 0, or -1 on bad
- * arguments or a device failure (then no output is meaningful). */
+ * `device`, or for device = -1 spread over the bcc_set_devices() GPUs; a round of at most
+ * bcc_set_host_small_round() checks runs on the host CPU.  Returns 0, or -1 on bad arguments, or
+ * -1 on a device failure under BCC_DEVICE_FAILURE_ERROR (then no output is meaningful; under the
+ * default policy the failed round is verified on the host and the call returns its exact result:
+ * "the Taproot side's failure handling" below). */
 int bcc_taproot_verify_batch(const bcc_taproot_check* items, size_t n, int* ret_out,
                              int* serror_out, unsigned char* sighash_out, int device);
 
@@ -117,7 +123,8 @@ typedef struct bcc_taproot_commit {
  * bcc_set_host_small_round() items run the same lane code on the host.  Results never depend on
  * the device set, the round cut or the thread count.  Returns 0 (also for n == 0), or -1 for null
  * arrays, an item with a null control, program32 or (with script_len > 0) script: nothing is
- * verified then; or -1 on a device failure (then no output is meaningful). */
+ * verified then; or -1 on a device failure under BCC_DEVICE_FAILURE_ERROR (then no output is
+ * meaningful; under the default policy the failed round runs the same lane code on the host). */
 int bcc_taproot_commit_batch(const bcc_taproot_commit* items, size_t n, int* ret_out,
                              int* serror_out, unsigned char* tapleaf_out, int device);
 
@@ -169,12 +176,27 @@ typedef struct bcc_taproot_spend {
  * that meets exactly one is run with both verdicts and reported when both runs agree (a lone
  * OP_CHECKSIG only pushes its verdict: WITNESS_MALLEATED either way); any other gets ret -1.
  * Synchronous on `device`, or for device = -1 spread in contiguous ranges over the
- * bcc_set_devices() GPUs; batches of at most bcc_set_host_small_round() items run the commitment
- * lane code on the host.  Adjacent items with the same tx and spent_outputs pointers share the
- * per-tx work.  Results never depend on the device set, the round cut or the thread count.
- * Returns 0 (also for n == 0), -1 for null arrays or an item with a null tx or spent_outputs
- * (nothing is verified then), or -1 on a device failure (then no output is meaningful; a failed
- * device round is not retried on the host). */
+ * bcc_set_devices() GPUs; a round of at most bcc_set_host_small_round() checks (signature checks
+ * plus commitments) runs on the host CPU altogether: the commitment lane code and the kernels'
+ * BIP340 lane, with no device state touched.  Adjacent items with the same tx and spent_outputs
+ * pointers share the per-tx work.  Results never depend on the device set, the round cut, the
+ * thread count or bcc_set_host_small_round.  Returns 0 (also for n == 0), -1 for null arrays or an
+ * item with a null tx or spent_outputs (nothing is verified then), or -1 on a device failure under
+ * BCC_DEVICE_FAILURE_ERROR (then no output is meaningful).
+ *
+ * The Taproot side's failure handling (this entry, bcc_taproot_verify_batch,
+ * bcc_taproot_commit_batch, mi_schnorr_verify_tuples, mi_xonly_tweak_check_tuples, and through
+ * them bcc_verify_inputs_batch / bcc_verify_input) is bitcoinconsensus_verify_batch's: a device
+ * round that fails with a transient HIP error (out of memory, not ready, a staging limit) is
+ * re-run once on a fresh context; if it fails again, or the error leaves the context unusable,
+ * bcc_set_device_failure_policy decides.  Under BCC_DEVICE_FAILURE_HOST (the default) the round is
+ * rebuilt from its items and verified on the host CPU by the engine's own code (host SHA-256 over
+ * the very job records the kernels read, the kernels' BIP340 and commitment lanes over the host
+ * comb), logged on stderr and counted by bcc_host_fallback_rounds; after an error that leaves the
+ * context unusable the call's remaining rounds on that device go the same way without another
+ * launch, and the entry returns its exact result.  Under BCC_DEVICE_FAILURE_ERROR the entry
+ * returns its error.  bcc_debug_fail_device_rounds reaches every one of these rounds, before it
+ * is launched. */
 int bcc_taproot_spend_batch(const bcc_taproot_spend* items, size_t n, int* ret_out,
                             int* serror_out, int device);
 /* Items per device round of bcc_taproot_spend_batch (0, the default: the engine's choice, 65,536).
@@ -219,8 +241,11 @@ typedef bcc_taproot_spend bcc_input;
  * Returns the number of valid items (0 for n == 0), or -1 for a null items or ret_out or an item
  * with a null tx or spent_outputs (nothing is verified then), or -1 when a device round failed:
  * the non-v1 side follows bcc_set_device_failure_policy exactly as bitcoinconsensus_verify_batch
- * does (its unfinished items carry BCC_ERR_DEVICE_FAILURE); the v1 side has no host path, so after
- * its failure no output is meaningful.  Both sides use the devices of bcc_set_device /
+ * does (its unfinished items carry BCC_ERR_DEVICE_FAILURE), and so does the v1 side: under
+ * BCC_DEVICE_FAILURE_HOST a failed round of either side is verified on the host and the call
+ * returns its exact result; under BCC_DEVICE_FAILURE_ERROR the items a failed round of either side
+ * left without a verdict get ret 0 / BCC_ERR_DEVICE_FAILURE while every other item keeps its
+ * result.  Both sides use the devices of bcc_set_device /
  * bcc_set_devices.  Results never depend on the device set, bcc_set_pipeline_chunk,
  * bcc_set_spend_round or the thread count.  Synchronous.  A call with items for both sides runs them
  * at the same time: the non-v1 subset on the calling thread, the v1 subset on a second thread that
@@ -229,8 +254,10 @@ typedef bcc_taproot_spend bcc_input;
 long bcc_verify_inputs_batch(const bcc_input* items, size_t n, unsigned int flags, int* ret_out,
                              int* err_out);
 /* One input: ret, and *err when err != NULL.  A null tx or spent_outputs counts as an empty buffer.
- * Where the batch call would return -1 for a failed device round there is no verdict, and the call
- * aborts as bitcoinconsensus_verify_script_with_amount does. */
+ * A lone input is a small round (bcc_set_host_small_round): it is verified on the host CPU and opens
+ * no device.  Where the batch call would return -1 for a failed device round (only under
+ * BCC_DEVICE_FAILURE_ERROR: the default policy verifies such a round on the host) there is no
+ * verdict, and the call aborts as bitcoinconsensus_verify_script_with_amount does. */
 int bcc_verify_input(const unsigned char* tx, unsigned int tx_len,
                      const unsigned char* spent_outputs, unsigned int spent_outputs_len,
                      unsigned int n_in, unsigned int flags, int* err);
@@ -244,6 +271,19 @@ typedef struct bcc_inputs_stats {
 /* Statistics of the calling thread's last bcc_verify_inputs_batch / bcc_verify_input call. */
 void bcc_last_inputs_stats(bcc_inputs_stats* out);
 
+/* Where the Taproot side's work ran. */
+typedef struct bcc_taproot_stats {
+    size_t items, checks, commits;   /* signature rows and commitment lanes of the call */
+    size_t rounds, host_rounds;      /* host_rounds: small rounds + failure fallbacks   */
+    size_t host_checks;              /* rows + commitments the host verified            */
+    size_t device_retries;
+} bcc_taproot_stats;
+/* Statistics of the calling thread's last Taproot-side call: bcc_taproot_verify_batch,
+ * bcc_taproot_spend_batch, bcc_taproot_commit_batch, mi_schnorr_verify_tuples,
+ * mi_xonly_tweak_check_tuples, or the v1 side of bcc_verify_inputs_batch / bcc_verify_input (a
+ * call without v1 items leaves them as they were). */
+void bcc_last_taproot_stats(bcc_taproot_stats* out);
+
 /* The layer below (the role mi_schnorr_verify_tuples has for signatures): n rows of the tweaked
  * key q, the parity byte, the internal key p and the tweak t (32-byte big-endian strings).
  * verdict[i] = 1 iff secp256k1_xonly_pubkey_parse(internal32_i) succeeds and
@@ -251,7 +291,8 @@ void bcc_last_inputs_stats(bcc_inputs_stats* out);
  * (secp256k1/src/modules/extrakeys/main_impl.h:21-41, 109-129); a parity byte other than 0 or 1
  * gives 0.  Synchronous on `device` (-1: spread over the bcc_set_devices() GPUs); at most
  * bcc_set_host_small_round() rows run on the host.  Returns 0, -1 for null arrays, or a HIP error
- * code on a device failure. */
+ * code on a device failure under BCC_DEVICE_FAILURE_ERROR (the default policy runs a failed
+ * round's rows through the same lane code on the host). */
 int mi_xonly_tweak_check_tuples(const uint8_t* tweaked32, const uint8_t* parity,
                                 const uint8_t* internal32, const uint8_t* tweak32,
                                 uint8_t* verdict, size_t n, int device);
@@ -456,7 +497,9 @@ void bcc_last_sighash_kinds(bcc_sighash_kinds* out);
  *                            entry point returns its normal, exact result;
  *   BCC_DEVICE_FAILURE_ERROR (BCC_DEVICE_FAILURE=error) bitcoinconsensus_verify_batch returns -1
  *                            (unfinished items: BCC_ERR_DEVICE_FAILURE) and the single-item ABI
- *                            aborts, as there is no verdict (see bitcoinconsensus.h). */
+ *                            aborts, as there is no verdict (see bitcoinconsensus.h).
+ * The Taproot entries follow the same rules with their own host evaluation
+ * (csrc/host/taproot_host.cpp; see bcc_taproot_spend_batch). */
 #define BCC_DEVICE_FAILURE_HOST 0
 #define BCC_DEVICE_FAILURE_ERROR 1
 int bcc_set_device_failure_policy(int policy);
@@ -464,7 +507,9 @@ int bcc_set_device_failure_policy(int policy);
  * engine's own lane code instead of the GPU (default BCC_HOST_SMALL_ROUND_DEFAULT, or the
  * BCC_HOST_SMALL_ROUND environment variable; 0: every round on the GPU).  One lane of the GPU
  * ladder is a single wave issuing a few hundred thousand dependent instructions, so a lone
- * verify() costs ~1.6 ms as a GPU round and ~0.1 ms on the host. */
+ * verify() costs ~1.6 ms as a GPU round and ~0.1 ms on the host.  The Taproot entries apply the
+ * same threshold to their rounds (signature checks plus commitments); the figures measured for
+ * them are in DESIGN.md 3.16. */
 #define BCC_HOST_SMALL_ROUND_DEFAULT 16
 int bcc_set_host_small_round(size_t tuples);
 /* Device rounds (or per-GPU groups) verified on the host after a device failure, process-wide. */
@@ -472,11 +517,16 @@ size_t bcc_host_fallback_rounds(void);
 /* mi_ecdsa_verify_tuples' contract on the host CPU (threads >= 1). */
 int bcc_host_verify_tuples(const uint8_t* pub65, const uint8_t* msg32, const uint8_t* r32,
                            const uint8_t* s32, uint8_t* verdict, size_t n, unsigned threads);
+/* mi_schnorr_verify_tuples' contract on the host CPU (threads >= 1): the kernels' BIP340 lane. */
+int bcc_host_schnorr_verify_tuples(const uint8_t* sig64, const uint8_t* msg32,
+                                   const uint8_t* xonly32, uint8_t* verdict, size_t n,
+                                   unsigned threads);
 
 /* Fault injection (tests): the next `rounds` device rounds of any thread fail as if the HIP
  * runtime had returned a transient error (hipErrorOutOfMemory), without touching the GPU (also:
  * BCC_FAULT_INJECT=rounds in the environment at load time); _code injects the given HIP error
- * (e.g. 719, hipErrorLaunchFailure: sticky, never retried). */
+ * (e.g. 719, hipErrorLaunchFailure: sticky, never retried).  Every device round of every entry
+ * point counts, the Taproot ones included. */
 void bcc_debug_fail_device_rounds(int rounds);
 void bcc_debug_fail_device_rounds_code(int rounds, int hip_error);
 /* Test hook: signature-kernel scratch requests above `lanes` lanes fail as out of memory (0: no

@@ -645,6 +645,39 @@ def host_verify_tuples(pub65, msg32, r32, s32, threads=1):
     return out.raw[:n]
 
 
+def host_schnorr_verify_tuples(sig64, msg32, xonly32, threads=1, library=None):
+    """bcc_host_schnorr_verify_tuples: mi_schnorr_verify_tuples' contract on the host CPU (the
+    kernels' BIP340 lane).  `library`: another build of the same C ABI."""
+    n = len(msg32) // 32
+    out = ctypes.create_string_buffer(max(1, n))
+    L = library if library is not None else lib()
+    u8p = ctypes.c_char_p
+    L.bcc_host_schnorr_verify_tuples.argtypes = [u8p, u8p, u8p, u8p, ctypes.c_size_t, ctypes.c_uint]
+    if L.bcc_host_schnorr_verify_tuples(bytes(sig64), bytes(msg32), bytes(xonly32), out, n,
+                                        threads) != 0:
+        raise RuntimeError("bcc_host_schnorr_verify_tuples failed")
+    return out.raw[:n]
+
+
+class TaprootStats(ctypes.Structure):
+    """include/bcc_amd.h bcc_taproot_stats."""
+    _fields_ = [(k, ctypes.c_size_t) for k in ("items", "checks", "commits", "rounds",
+                                               "host_rounds", "host_checks", "device_retries")]
+
+
+def last_taproot_stats(library=None):
+    """bcc_last_taproot_stats: where the calling thread's last Taproot-side call ran
+    (taproot_verify_batch, taproot_spend_batch, taproot_commit_batch, the tuple entries, or the v1
+    side of verify_inputs_batch / verify_input).  host_rounds counts small rounds and failure
+    fallbacks alike; host_fallback_rounds() counts only the latter."""
+    s = TaprootStats()
+    L = library if library is not None else lib()
+    L.bcc_last_taproot_stats.argtypes = [ctypes.POINTER(TaprootStats)]
+    L.bcc_last_taproot_stats.restype = None
+    L.bcc_last_taproot_stats(ctypes.byref(s))
+    return {k: getattr(s, k) for k, _ in TaprootStats._fields_}
+
+
 def set_device(device):
     lib().bcc_set_device(device)
 

@@ -49,6 +49,9 @@
 #include "ecdsa_lane.h"
 #include "ecdsa_twist.h"
 #include "gpu_common.h"
+#include "host/devices.h"
+#include "host/host_verify.h"
+#include "host/taproot_host.h"
 #include "pipeline.h"
 
 namespace bcc {
@@ -1223,6 +1226,10 @@ int tuple_thread_buffers(int device, size_t dbytes, size_t hbytes, void** dbuf, 
     return 0;
 }
 
+void tuple_thread_drop(int device) {
+    if (device >= 0 && device < 64) tl_ctx[device].reset();
+}
+
 // The current device's comb tables (device_tables) for kernels outside this file.
 int comb_device_tables(int* dev, const uint32_t** gcomb, int* cus) {
     return device_tables(dev, gcomb, cus);
@@ -1264,10 +1271,9 @@ int mi_schnorr_verify_device(const uint8_t* d_sig64, const uint8_t* d_msg32,
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// BIP340 host-buffer entry: n rows of sig64 / msg32 / xonly32; synchronous on `device`.
-int mi_schnorr_verify_tuples(const uint8_t* sig64, const uint8_t* msg32, const uint8_t* xonly32,
-                             uint8_t* verdict, size_t n, int device) {
-    if (n == 0) return 0;
+// One device round of n BIP340 rows on the calling thread's context.
+static int schnorr_tuples_device(const uint8_t* sig64, const uint8_t* msg32, const uint8_t* xonly32,
+                                 uint8_t* verdict, size_t n, int device) {
     BCC_HIP_TRY(hipSetDevice(device));
     ThreadCtx* ctx = nullptr;
     if (int e = thread_ctx(device, &ctx)) return e;
@@ -1289,6 +1295,33 @@ int mi_schnorr_verify_tuples(const uint8_t* sig64, const uint8_t* msg32, const u
     }
     memcpy(verdict, h + o_v, n);
     return 0;
+}
+
+// BIP340 host-buffer entry: n rows of sig64 / msg32 / xonly32; synchronous on `device`.  At most
+// host_small_round() rows run the same lane on the host; a round the device cannot deliver is
+// retried once and then goes to the failure policy (host/taproot_host.h).
+int mi_schnorr_verify_tuples(const uint8_t* sig64, const uint8_t* msg32, const uint8_t* xonly32,
+                             uint8_t* verdict, size_t n, int device) {
+    if (n == 0) return 0;
+    host::TaprootCounters counters;
+    const auto on_host = [&] {
+        host::host_schnorr_rows(sig64, msg32, xonly32, verdict, n, host::host_threads());
+    };
+    int rc = 0;
+    if (n <= host::host_small_round()) {
+        on_host();
+        counters.round(n, 0, true);
+    } else {
+        host::DeviceRange range;
+        rc = host::resilient_taproot_round("mi_schnorr_verify_tuples", device, n, 0, range, counters,
+                                           [&] {
+            const int e = schnorr_tuples_device(sig64, msg32, xonly32, verdict, n, device);
+            if (e) tuple_thread_drop(device);  // wherever it failed: a re-run gets a fresh context
+            return e;
+        }, on_host);
+    }
+    host::taproot_stats_store(n, counters);
+    return rc;
 }
 
 // Host-buffer entry (the inner C ABI of SURVEY §8b): pub65[n] = header byte || x || y (y ignored

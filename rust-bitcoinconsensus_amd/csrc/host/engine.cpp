@@ -1280,6 +1280,7 @@ int device_round(int dev, const SighashJobs* const* pj, const TupleRows* const* 
 }  // namespace
 
 int injected_device_fault() { return take_injected_fault(); }
+bool retryable_device_error(int hip_error) { return retryable(hip_error); }
 
 int resilient_round(int dev, const SighashJobs* const* pj, const TupleRows* const* pr, size_t P,
                     uint8_t* verdict, double* stage_s, size_t* retries, size_t* host_rounds,

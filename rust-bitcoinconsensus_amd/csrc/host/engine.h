@@ -44,6 +44,9 @@ void append_round(SighashJobs& dst, TupleRows& dst_rows, const SighashJobs& src,
 // A pending bcc_debug_fail_device_rounds fault, consumed (its HIP error code), else 0: the staged
 // rounds (tuples.cpp) take it as a failed staging, as device_round does for a failed round.
 int injected_device_fault();
+// Whether a HIP error is worth one retry on a fresh device context (allocation / readiness
+// trouble); any other error leaves the context unusable.
+bool retryable_device_error(int hip_error);
 
 // One device round of P parts on `dev` with the engine's failure handling: one retry on a fresh
 // device batch for a transient HIP error (*retries), then the device failure policy: the parts are
@@ -58,8 +61,9 @@ int resilient_round(int dev, const SighashJobs* const* pj, const TupleRows* cons
 // Frees the calling thread's Taproot job buffers (host/taproot.cpp).
 void taproot_release_thread_state();
 
-// The SigMsg digests of a part's device-built Taproot jobs computed on the host (the CPU twin of
-// sighash.hip taproot_tx_kernel + taproot_msg_kernel: tests, stub device): msg + 32 row.
+// The SigMsg digests of a part's device-built Taproot jobs computed on the host (taproot_host.cpp:
+// the CPU twin of sighash.hip taproot_tx_kernel + taproot_msg_kernel, part of the host evaluation
+// of a Taproot round; the CPU tests' stub device calls it too): msg + 32 row.
 void taproot_dev_sigmsg_host(const TaprootTxJobs& jobs, uint8_t* msg);
 
 }  // namespace host

@@ -34,6 +34,7 @@
 #include "bcc_amd.h"
 #include "devices.h"
 #include "inputs.h"
+#include "taproot_host.h"
 #include "team.h"
 #include "tuples.h"
 #include "tx.h"
@@ -229,17 +230,27 @@ long run_inputs(const bcc_input* items, size_t n, unsigned flags, int* ret_out, 
 
     long status = 0, valid = 0;
     std::vector<int> r, e;
+    // One v1 item's answer: VerifyScript's verdict, or, where a failed device round left none
+    // (BCC_DEVICE_FAILURE_ERROR), ret 0 / BCC_ERR_DEVICE_FAILURE as the other side reports it.
+    auto scatter_spend = [&](size_t i, int ret, uint8_t no_verdict) {
+        ret_out[i] = !no_verdict && ret == 1 ? 1 : 0;
+        if (err_out) err_out[i] = no_verdict ? BCC_ERR_DEVICE_FAILURE : bitcoinconsensus_ERR_OK;
+        valid += !no_verdict && ret == 1;
+    };
     if (ne && np) {
         const auto t1 = clk::now();
         std::vector<int> rt(np), et(np);
+        std::vector<uint8_t> unfinished(np, 0);
         r.resize(ne);
         e.resize(ne);
         int rc_t = 0;
         double taproot_s = 0;
+        bcc_taproot_stats side_stats{};
         if (!tl_side) tl_side.reset(new SideWorker());
         tl_side->start([&] {
             const auto t2 = clk::now();
-            rc_t = bcc_taproot_spend_batch(spends.data(), np, rt.data(), et.data(), -1);
+            rc_t = taproot_spend_run(spends.data(), np, rt.data(), et.data(), -1, unfinished.data());
+            bcc_last_taproot_stats(&side_stats);  // that thread's last call: handed to the caller
             taproot_s = since(t2);
         });
         long rc = -1;
@@ -251,6 +262,7 @@ long run_inputs(const bcc_input* items, size_t n, unsigned flags, int* ret_out, 
         st.ecdsa_side_seconds = since(t1);
         tl_side->wait();  // (before anything the job refers to leaves scope)
         st.taproot_side_seconds = taproot_s;
+        taproot_stats_set(side_stats);
         if (rc < 0 || rc_t != 0) status = -1;
         // (rule 2 passed, so err is OK, or BCC_ERR_DEVICE_FAILURE where the device left no verdict)
         for (size_t k = 0; k < ne; k++) {
@@ -261,11 +273,7 @@ long run_inputs(const bcc_input* items, size_t n, unsigned flags, int* ret_out, 
         // ret -1 after rules 1-3: a scriptSig whose result hangs on ECDSA verdicts.  It is invalid
         // under every verdict (its own script error, or WITNESS_MALLEATED), and the script error is
         // not part of this contract.
-        for (size_t k = 0; k < np; k++) {
-            ret_out[spend_idx[k]] = rt[k] == 1 ? 1 : 0;
-            if (err_out) err_out[spend_idx[k]] = bitcoinconsensus_ERR_OK;
-            valid += rt[k] == 1;
-        }
+        for (size_t k = 0; k < np; k++) scatter_spend(spend_idx[k], rt[k], unfinished[k]);
         st.total_seconds = since(t0);
         return status < 0 ? -1 : valid;
     }
@@ -288,12 +296,10 @@ long run_inputs(const bcc_input* items, size_t n, unsigned flags, int* ret_out, 
         const auto t1 = clk::now();
         r.resize(np);
         e.resize(np);
-        if (bcc_taproot_spend_batch(spends.data(), np, r.data(), e.data(), -1) != 0) status = -1;
-        for (size_t k = 0; k < np; k++) {  // (ret -1: see above)
-            ret_out[spend_idx[k]] = r[k] == 1 ? 1 : 0;
-            if (err_out) err_out[spend_idx[k]] = bitcoinconsensus_ERR_OK;
-            valid += r[k] == 1;
-        }
+        std::vector<uint8_t> unfinished(np, 0);
+        if (taproot_spend_run(spends.data(), np, r.data(), e.data(), -1, unfinished.data()) != 0)
+            status = -1;
+        for (size_t k = 0; k < np; k++) scatter_spend(spend_idx[k], r[k], unfinished[k]);  // (ret -1: see above)
         st.taproot_side_seconds = since(t1);
     }
     st.total_seconds = since(t0);
@@ -339,8 +345,9 @@ int bcc_verify_input(const unsigned char* tx, unsigned int tx_len, const unsigne
                          spent_outputs ? spent_outputs_len : 0u, n_in};
     int ret = 0, e = bitcoinconsensus_ERR_OK;
     if (bcc_verify_inputs_batch(&item, 1, flags, &ret, &e) < 0) {
-        // no verdict (a failed device round): as bitcoinconsensus_verify_script_with_amount, the
-        // single-item call has no code for it and must not report a consensus failure
+        // no verdict (a failed device round under BCC_DEVICE_FAILURE_ERROR; the default policy
+        // verifies such a round on the host CPU): as bitcoinconsensus_verify_script_with_amount,
+        // the single-item call has no code for it and must not report a consensus failure
         fprintf(stderr, "[bcc] bcc_verify_input: GPU unavailable, no verdict; aborting\n");
         abort();
     }

@@ -9,8 +9,9 @@
 // runs twice.  What is left for the device per round: the script-path commitments (which also
 // yield the TapLeaf hashes the recorded checks' signature hashes need) and every signature check,
 // key path and tapscript together.  The device round is reached through g_spend_device_hook
-// (taproot_spend.h); without one, and for small batches, round_host composes the commitment lane
-// code (taproot_commit.h) with gpu_taproot_verify_parts.
+// (taproot_spend.h); without one, round_host composes the commitment lane code (taproot_commit.h)
+// with gpu_taproot_verify_parts.  A small round, and a round the device could not deliver, runs on
+// the host CPU altogether: the same lane code and host_taproot_parts (taproot_host.h).
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -23,6 +24,7 @@
 #include "host_verify.h"
 #include "script.h"
 #include "taproot_commit.h"
+#include "taproot_host.h"
 #include "taproot_jobs.h"
 #include "taproot_spend.h"
 #include "team.h"
@@ -243,9 +245,11 @@ void build_part(const bcc_taproot_spend* items, size_t lo, size_t hi, int* ret, 
 const GCombArray host_comb() { return GCombArray{static_cast<const fe*>(host_comb_tables())}; }
 
 // A round without the fused device path: every commitment on the host lanes (the kernels' lane
-// code), the TapLeaf hashes copied into the checks' slots, then the signature parts through the
-// device seam the engine has always had.
-int round_host(int device, const SpendRound& R, uint8_t* commit_verdict, uint8_t* sig_verdict) {
+// code), the TapLeaf hashes copied into the checks' slots, then the signature parts: on the host
+// too (sigs_on_host: a small round, or a round the device could not deliver), or through the
+// device seam the engine has always had (a build without the fused round).
+int round_host(int device, const SpendRound& R, uint8_t* commit_verdict, uint8_t* sig_verdict,
+               bool sigs_on_host) {
     static const CommitMids mids = commit_mids();
     const GCombArray gc = host_comb();
     std::vector<size_t> c0(R.P + 1, 0);
@@ -278,6 +282,10 @@ int round_host(int device, const SpendRound& R, uint8_t* commit_verdict, uint8_t
     if (rows == 0) return 0;
     std::vector<const TaprootJobs*> pj;
     for (size_t q = 0; q < R.P; q++) pj.push_back(&R.parts[q]->jobs);
+    if (sigs_on_host) {
+        host_taproot_parts(pj.data(), pj.size(), sig_verdict, nullptr, host_threads());
+        return 0;
+    }
     return gpu_taproot_verify_parts(device, pj.data(), pj.size(), sig_verdict, nullptr);
 }
 
@@ -299,31 +307,32 @@ void apply_round(const RoundOut& o, int* ret, int* serr) {
 }
 
 // Items [lo, hi) on `device` in rounds that rotate over the Taproot contexts: round k's host pass
-// runs while rounds k - 1 and k - 2 are on the GPU, and its upload beside their kernels.
+// runs while rounds k - 1 and k - 2 are on the GPU, and its upload beside their kernels.  A round of
+// at most host_small_round() checks (signature rows + commitments) runs on the host and touches no
+// device state.  A round the device cannot deliver (an injected fault, a failed begin or end) is
+// rebuilt from its items, re-run once if the error is transient, and else left to the failure
+// policy: verified on the host, or (BCC_DEVICE_FAILURE_ERROR) its items marked in `unfinished`
+// (optional, one byte per item) together with every item of the range not yet decided.
 int run_range(const bcc_taproot_spend* items, size_t lo, size_t hi, int* ret, int* serr, int device,
-              bool on_host) {
-    const SpendDeviceHook* hook = on_host ? nullptr : g_spend_device_hook;
+              TaprootCounters& c, uint8_t* unfinished) {
+    constexpr const char* WHO = "taproot_spend_batch";
+    const SpendDeviceHook* hook = g_spend_device_hook;
     const size_t set_round = g_spend_round.load(std::memory_order_relaxed);
     const size_t RS = set_round ? set_round : SPEND_ROUND_DEFAULT;
     std::vector<SpendPart> parts;
     std::vector<PartMeta> metas;
+    std::vector<SpendPart*> pp;
     RoundOut outs[TAPROOT_SLOTS];
-    std::vector<int> inflight;
-    int err = 0;
-    auto finish = [&](int slot) {
-        RoundOut& o = outs[slot];
-        o.commit_verdict.assign(o.item_of_commit.size() + 1, 0);
-        o.sig_verdict.assign(o.item_of_row.size() + 1, 0);
-        const int e = hook->end(device, slot, o.commit_verdict.data(), o.sig_verdict.data());
-        if (e == 0) apply_round(o, ret, serr);
-        return e;
+    struct Flight {
+        int slot;
+        size_t lo, hi;  // its item range: a failed round is rebuilt from it
     };
-    // slots rotate by LAUNCHED rounds: at most TAPROOT_SLOTS - 1 are in flight after a launch, so
-    // the next launch's slot is never one of them (a round without device work launches nothing
-    // and must not advance the rotation)
-    size_t launched = 0;
-    for (size_t a = lo; a < hi && !err; a += RS) {
-        const size_t b = std::min(hi, a + RS);
+    std::vector<Flight> inflight;
+    DeviceRange fail;
+    int err = 0;
+    // The host pass of items [a, b) into parts / metas, and the round's item maps and verdict
+    // buffers into o.  Returns 0 (no device work), 1, or -1 (blobs beyond the 32-bit offsets).
+    auto build = [&](size_t a, size_t b, RoundOut& o) -> int {
         const unsigned T = pool_threads(b - a, 1024);
         if (parts.size() < T) {
             parts.resize(T);
@@ -333,58 +342,159 @@ int run_range(const bcc_taproot_spend* items, size_t lo, size_t hi, int* ret, in
             build_part(items, a + (b - a) * t / T, a + (b - a) * (t + 1) / T, ret, serr, parts[t],
                        metas[t]);
         });
-        size_t raw = 0, ext = 0, work = 0;
-        for (unsigned t = 0; t < T; t++) {
-            work += metas[t].item_of_row.size() + metas[t].item_of_commit.size();
-            raw += parts[t].jobs.dev.txraw.size();
-            ext += parts[t].jobs.dev.ext.size();
-        }
-        if (work == 0) continue;  // decided on the host: no slot is touched
-        const int slot = (int)(launched % TAPROOT_SLOTS);
-        RoundOut& o = outs[slot];  // free: its last round was finished before two later launches
+        size_t raw = 0, ext = 0;
         o.item_of_row.clear();
         o.item_of_commit.clear();
-        std::vector<SpendPart*> pp;
+        pp.clear();
         for (unsigned t = 0; t < T; t++) {
             pp.push_back(&parts[t]);
             o.item_of_row.insert(o.item_of_row.end(), metas[t].item_of_row.begin(), metas[t].item_of_row.end());
             o.item_of_commit.insert(o.item_of_commit.end(), metas[t].item_of_commit.begin(),
                                     metas[t].item_of_commit.end());
+            raw += parts[t].jobs.dev.txraw.size();
+            ext += parts[t].jobs.dev.ext.size();
         }
+        o.commit_verdict.assign(o.item_of_commit.size() + 1, 0);
+        o.sig_verdict.assign(o.item_of_row.size() + 1, 0);
+        if (o.item_of_row.empty() && o.item_of_commit.empty()) return 0;
         if (raw >= ((size_t)1 << 32) || ext >= ((size_t)1 << 32)) {
             fprintf(stderr, "[bcc] bcc_taproot_spend_batch: a round's blobs exceed 4 GiB; lower bcc_set_spend_round\n");
+            return -1;
+        }
+        return 1;
+    };
+    auto give_up = [&](const RoundOut& o) {  // no verdict for this round's items
+        if (!unfinished) return;
+        for (uint32_t i : o.item_of_row) unfinished[i] = 1;
+        for (uint32_t i : o.item_of_commit) unfinished[i] = 1;
+    };
+    auto on_host = [&](RoundOut& o) {  // the round in parts / o, all of it on the host CPU
+        const SpendRound R{pp.data(), pp.size()};
+        round_host(device, R, o.commit_verdict.data(), o.sig_verdict.data(), true);
+        c.round(o.item_of_row.size(), o.item_of_commit.size(), true);
+        apply_round(o, ret, serr);
+    };
+    // Round f failed with e at its begin (parts still hold its own host pass) or at its end (by
+    // then they hold a later round's, so the round is rebuilt from its items: the pass is
+    // deterministic).
+    auto recover = [&](const Flight& f, int e, bool parts_intact) -> int {
+        RoundOut& o = outs[f.slot];
+        FailedRound r;
+        if (!parts_intact) r.rebuild = [&] { build(f.lo, f.hi, o); };
+        r.checks = [&] { return o.item_of_row.size() + o.item_of_commit.size(); };
+        r.run = [&] {
+            const SpendRound R{pp.data(), pp.size()};
+            if (int e2 = hook->begin(device, f.slot, R)) return e2;
+            return hook->end(device, f.slot, o.commit_verdict.data(), o.sig_verdict.data());
+        };
+        r.host = [&] {
+            const SpendRound R{pp.data(), pp.size()};
+            round_host(device, R, o.commit_verdict.data(), o.sig_verdict.data(), true);
+        };
+        r.done = [&](bool on_host) {
+            c.round(o.item_of_row.size(), o.item_of_commit.size(), on_host);
+            apply_round(o, ret, serr);
+        };
+        r.lost = [&] { give_up(o); };
+        return recover_round(WHO, device, e, fail, c, r);
+    };
+    auto finish = [&](const Flight& f) -> int {
+        RoundOut& o = outs[f.slot];
+        if (int e = hook->end(device, f.slot, o.commit_verdict.data(), o.sig_verdict.data()))
+            return recover(f, e, false);
+        c.round(o.item_of_row.size(), o.item_of_commit.size(), false);
+        apply_round(o, ret, serr);
+        return 0;
+    };
+    // slots rotate by LAUNCHED rounds: at most TAPROOT_SLOTS - 1 are in flight after a launch, so
+    // the next launch's slot is never one of them (a round without device work launches nothing
+    // and must not advance the rotation)
+    size_t launched = 0, a = lo;
+    for (; a < hi && !err; a += RS) {
+        const size_t b = std::min(hi, a + RS);
+        const int slot = (int)(launched % TAPROOT_SLOTS);
+        RoundOut& o = outs[slot];  // free: its last round was finished before two later launches
+        const int work = build(a, b, o);
+        if (work == 0) continue;  // decided on the host: no slot is touched
+        if (work < 0) {
+            give_up(o);
             err = -1;
+            a += RS;
             break;
         }
         const SpendRound R{pp.data(), pp.size()};
-        if (!hook) {
-            o.commit_verdict.assign(o.item_of_commit.size() + 1, 0);
-            o.sig_verdict.assign(o.item_of_row.size() + 1, 0);
-            err = round_host(device, R, o.commit_verdict.data(), o.sig_verdict.data());
-            if (!err) apply_round(o, ret, serr);
+        if (o.item_of_row.size() + o.item_of_commit.size() <= host_small_round()) {
+            on_host(o);
             continue;
         }
-        err = hook->begin(device, slot, R);
-        if (!err) {
-            inflight.push_back(slot);
+        if (!hook) {  // (a build without the fused round: commitment lanes + the signature seam)
+            err = resilient_taproot_round(WHO, device, o.item_of_row.size(), o.item_of_commit.size(),
+                                          fail, c, [&] {
+                return round_host(device, R, o.commit_verdict.data(), o.sig_verdict.data(), false);
+            }, [&] {
+                round_host(device, R, o.commit_verdict.data(), o.sig_verdict.data(), true);
+            });
+            if (!err) apply_round(o, ret, serr);
+            else give_up(o);
+            continue;
+        }
+        // an injected fault, or an earlier error that left the context unusable, comes before the
+        // launch: such a round never reaches the GPU
+        const Flight f{slot, a, b};
+        int e = round_blocked(fail);
+        if (!e) e = hook->begin(device, slot, R);
+        if (e) {
+            err = recover(f, e, true);
+        } else {
+            inflight.push_back(f);
             launched++;
         }
         while ((int)inflight.size() > TAPROOT_SLOTS - 1 || (err && !inflight.empty())) {
-            const int p = inflight.front();
+            const Flight p = inflight.front();
             inflight.erase(inflight.begin());
-            const int e = finish(p);
-            if (!err) err = e;
+            const int e2 = finish(p);
+            if (!err) err = e2;
         }
     }
-    for (int p : inflight) {  // in launch order; every launched round is finished, even after an error
-        const int e = finish(p);
+    for (const Flight& f : inflight) {  // in launch order; every launched round is ended, even after an error
+        const int e = finish(f);
         if (!err) err = e;
     }
-    if (err) fprintf(stderr, "[bcc] bcc_taproot_spend_batch failed on device %d: %d\n", device, err);
+    if (err) {
+        fprintf(stderr, "[bcc] bcc_taproot_spend_batch failed on device %d: %d\n", device, err);
+        if (unfinished)
+            for (size_t i = std::min(a, hi); i < hi; i++) unfinished[i] = 1;  // never built
+    }
     return err;
 }
 
 }  // namespace
+
+int taproot_spend_run(const bcc_taproot_spend* items, size_t n, int* ret_out, int* serror_out,
+                      int device, uint8_t* unfinished) {
+    if (n == 0) return 0;
+    if (!items || !ret_out || !serror_out) return -1;
+    for (size_t i = 0; i < n; i++)
+        if (!items[i].tx || !items[i].spent_outputs) return -1;
+    if (unfinished) memset(unfinished, 0, n);
+    ActiveCaller active;
+    std::vector<int> devs = device < 0 ? device_list() : std::vector<int>{device};
+    const size_t D = std::max<size_t>(1, std::min<size_t>(devs.size(), (n + 4095) / 4096));
+    devs.resize(D);
+    TaprootCounters counters;
+    std::vector<std::function<int()>> jobs;
+    for (size_t d = 0; d < D; d++) {
+        const size_t lo = n * d / D, hi = n * (d + 1) / D;
+        const int dev = devs[d];
+        jobs.push_back([=, &counters] {
+            return run_range(items, lo, hi, ret_out, serror_out, dev, counters, unfinished);
+        });
+    }
+    const int rc = run_on_devices(devs, jobs);
+    taproot_stats_store(n, counters);
+    return rc ? -1 : 0;
+}
+
 }  // namespace host
 }  // namespace bcc
 
@@ -395,22 +505,5 @@ extern "C" int bcc_set_spend_round(size_t items) {
 
 extern "C" int bcc_taproot_spend_batch(const bcc_taproot_spend* items, size_t n, int* ret_out,
                                        int* serror_out, int device) {
-    if (n == 0) return 0;
-    if (!items || !ret_out || !serror_out) return -1;
-    for (size_t i = 0; i < n; i++)
-        if (!items[i].tx || !items[i].spent_outputs) return -1;
-    bcc::host::ActiveCaller active;
-    const bool on_host = n <= bcc::host::host_small_round();
-    std::vector<int> devs = device < 0 ? bcc::host::device_list() : std::vector<int>{device};
-    const size_t D = std::max<size_t>(1, std::min<size_t>(devs.size(), (n + 4095) / 4096));
-    devs.resize(D);
-    std::vector<std::function<int()>> jobs;
-    for (size_t d = 0; d < D; d++) {
-        const size_t lo = n * d / D, hi = n * (d + 1) / D;
-        const int dev = devs[d];
-        jobs.push_back([=] {
-            return bcc::host::run_range(items, lo, hi, ret_out, serror_out, dev, on_host);
-        });
-    }
-    return bcc::host::run_on_devices(devs, jobs) ? -1 : 0;
+    return bcc::host::taproot_spend_run(items, n, ret_out, serror_out, device, nullptr);
 }

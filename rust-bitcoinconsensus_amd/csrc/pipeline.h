@@ -782,6 +782,9 @@ void release_tuple_thread_state();
 // The entries that use it are synchronous, so the buffers hold nothing between calls.
 int tuple_thread_buffers(int device, size_t dbytes, size_t hbytes, void** dbuf, void** hbuf,
                          void** stream);
+// Drops that context (stream, scratch, both buffers) after a round on it failed, whatever it still
+// had queued: the round's re-run starts from a fresh one.
+void tuple_thread_drop(int device);
 // The current device's fixed-base comb tables (ecdsa_twist.h layout) and CU count.
 int comb_device_tables(int* dev, const uint32_t** gcomb, int* cus);
 

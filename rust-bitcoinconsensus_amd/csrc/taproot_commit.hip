@@ -24,6 +24,7 @@
 #include "gpu_common.h"
 #include "host/devices.h"
 #include "host/host_verify.h"
+#include "host/taproot_host.h"
 #include "host/tuples.h"
 #include "pipeline.h"
 #include "taproot_commit.h"
@@ -255,9 +256,10 @@ void tuples_host(const uint8_t* q32, const uint8_t* par, const uint8_t* p32, con
     });
 }
 
-// One device's share of mi_xonly_tweak_check_tuples, in rounds of CURVE_CHUNK rows.
-int tuples_device(int device, const uint8_t* q32, const uint8_t* par, const uint8_t* p32,
-                  const uint8_t* t32, uint8_t* verdict, size_t n) {
+// One device's share of mi_xonly_tweak_check_tuples, in rounds of CURVE_CHUNK rows: rows
+// [first, first + count) (one round, or all of them with count = n).
+int tuples_rounds(int device, const uint8_t* q32, const uint8_t* par, const uint8_t* p32,
+                  const uint8_t* t32, uint8_t* verdict, size_t n, size_t first, size_t count) {
     const size_t R = std::min(n, CURVE_CHUNK);
     const size_t row = align256(32 * R), o_q = row, o_t = 2 * row, o_par = 3 * row,
                  o_v = o_par + align256(R), o_s = o_v + align256(R);
@@ -266,8 +268,8 @@ int tuples_device(int device, const uint8_t* q32, const uint8_t* par, const uint
     uint8_t* d = (uint8_t*)dv;
     uint8_t* h = (uint8_t*)hv;
     hipStream_t st = (hipStream_t)sv;
-    for (size_t lo = 0; lo < n; lo += R) {
-        const size_t m = std::min(R, n - lo);
+    for (size_t lo = first; lo < first + count; lo += R) {
+        const size_t m = std::min(R, first + count - lo);
         host::pfor(m, 1 << 15, [&](size_t a, size_t b) {  // into the page-locked image, on the team
             memcpy(h + 32 * a, p32 + 32 * (lo + a), 32 * (b - a));
             memcpy(h + o_q + 32 * a, q32 + 32 * (lo + a), 32 * (b - a));
@@ -286,6 +288,26 @@ int tuples_device(int device, const uint8_t* q32, const uint8_t* par, const uint
         }
         kt.collect();
         memcpy(verdict + lo, h + o_v, m);
+    }
+    return 0;
+}
+
+// The same share under the Taproot side's failure rules (host/taproot_host.h), round by round.
+int tuples_device(int device, const uint8_t* q32, const uint8_t* par, const uint8_t* p32,
+                  const uint8_t* t32, uint8_t* verdict, size_t n, host::TaprootCounters& counters) {
+    const size_t R = std::min(n, CURVE_CHUNK);
+    host::DeviceRange range;
+    for (size_t lo = 0; lo < n; lo += R) {
+        const size_t m = std::min(R, n - lo);
+        if (int e = host::resilient_taproot_round("mi_xonly_tweak_check_tuples", device, 0, m, range,
+                                                  counters, [&] {
+                const int e = tuples_rounds(device, q32, par, p32, t32, verdict, n, lo, m);
+                if (e) tuple_thread_drop(device);  // a re-run gets a fresh context
+                return e;
+            }, [&] {
+                tuples_host(q32 + 32 * lo, par + lo, p32 + 32 * lo, t32 + 32 * lo, verdict + lo, m);
+            }))
+            return e;
     }
     return 0;
 }
@@ -363,11 +385,13 @@ int commit_round(int device, const bcc_taproot_commit* items, size_t n, int* ret
 
 // One device's contiguous share, cut into rounds by item count and blob bytes.
 int commit_range(int device, const bcc_taproot_commit* items, size_t n, int* ret, int* serror,
-                 uint8_t* tapleaf) {
+                 uint8_t* tapleaf, host::TaprootCounters& counters) {
     if (n <= host::host_small_round()) {
         commit_host(items, n, ret, serror, tapleaf);
+        counters.round(0, n, true);
         return 0;
     }
+    host::DeviceRange range;
     for (size_t lo = 0; lo < n;) {
         size_t hi = lo, blob = 0;
         while (hi < n && hi - lo < COMMIT_ROUND_ITEMS) {
@@ -378,8 +402,13 @@ int commit_range(int device, const bcc_taproot_commit* items, size_t n, int* ret
             blob += b;
             hi++;
         }
-        if (int e = commit_round(device, items + lo, hi - lo, ret + lo, serror + lo,
-                                 tapleaf ? tapleaf + 32 * lo : nullptr)) {
+        uint8_t* const lh = tapleaf ? tapleaf + 32 * lo : nullptr;
+        if (int e = host::resilient_taproot_round("taproot_commit_batch", device, 0, hi - lo, range,
+                                                  counters, [&] {
+                const int e = commit_round(device, items + lo, hi - lo, ret + lo, serror + lo, lh);
+                if (e) tuple_thread_drop(device);  // a re-run gets a fresh context
+                return e;
+            }, [&] { commit_host(items + lo, hi - lo, ret + lo, serror + lo, lh); })) {
             fprintf(stderr, "[bcc] bcc_taproot_commit_batch failed on device %d: %d\n", device, e);
             return e;
         }
@@ -531,14 +560,19 @@ int mi_xonly_tweak_check_tuples(const uint8_t* tweaked32, const uint8_t* parity,
     if (n == 0) return 0;
     if (!tweaked32 || !parity || !internal32 || !tweak32 || !verdict) return -1;
     for (double& ms : tl_kernel_ms) ms = 0;
+    host::TaprootCounters counters;
+    int rc = 0;
     if (n <= host::host_small_round()) {
         tuples_host(tweaked32, parity, internal32, tweak32, verdict, n);
-        return 0;
+        counters.round(0, n, true);
+    } else {
+        rc = over_devices(device, n, [&](int dev, size_t lo, size_t hi) {
+            return tuples_device(dev, tweaked32 + 32 * lo, parity + lo, internal32 + 32 * lo,
+                                 tweak32 + 32 * lo, verdict + lo, hi - lo, counters);
+        });
     }
-    return over_devices(device, n, [&](int dev, size_t lo, size_t hi) {
-        return tuples_device(dev, tweaked32 + 32 * lo, parity + lo, internal32 + 32 * lo,
-                             tweak32 + 32 * lo, verdict + lo, hi - lo);
-    });
+    host::taproot_stats_store(n, counters);
+    return rc;
 }
 
 int bcc_taproot_commit_batch(const bcc_taproot_commit* items, size_t n, int* ret_out,
@@ -549,14 +583,18 @@ int bcc_taproot_commit_batch(const bcc_taproot_commit* items, size_t n, int* ret
         if (!items[i].control || !items[i].program32 || (!items[i].script && items[i].script_len))
             return -1;
     for (double& ms : tl_kernel_ms) ms = 0;
+    host::TaprootCounters counters;
+    int rc = 0;
     if (n <= host::host_small_round()) {
         commit_host(items, n, ret_out, serror_out, tapleaf_out);
-        return 0;
+        counters.round(0, n, true);
+    } else {
+        rc = over_devices(device, n, [&](int dev, size_t lo, size_t hi) {
+            return commit_range(dev, items + lo, hi - lo, ret_out + lo, serror_out + lo,
+                                tapleaf_out ? tapleaf_out + 32 * lo : nullptr, counters);
+        });
     }
-    const int rc = over_devices(device, n, [&](int dev, size_t lo, size_t hi) {
-        return commit_range(dev, items + lo, hi - lo, ret_out + lo, serror_out + lo,
-                            tapleaf_out ? tapleaf_out + 32 * lo : nullptr);
-    });
+    host::taproot_stats_store(n, counters);
     return rc ? -1 : 0;
 }
 
