@@ -771,14 +771,14 @@ static int device_tables(int* dev, const u32** gcomb, int* cus) {
 }
 
 SigScratch::~SigScratch() {
-    if (dev >= 0 && (sinv || chunk || qtab2 || ev_qa || ev_ga || aux)) {
+    if (dev >= 0 && (sinv.p || chunk || qtab2.p || ev_qa || ev_ga || aux)) {
         int cur = 0;
         (void)hipGetDevice(&cur);
         (void)hipSetDevice(dev);
         if (aux) (void)hipStreamSynchronize((hipStream_t)aux);
-        if (sinv) (void)hipFree(sinv);
+        (void)sinv.release();  // here, not after this body: on their device
         if (chunk) (void)hipFree(chunk);
-        if (qtab2) (void)hipFree(qtab2);
+        (void)qtab2.release();
         if (ev_qa) (void)hipEventDestroy((hipEvent_t)ev_qa);
         if (ev_ga) (void)hipEventDestroy((hipEvent_t)ev_ga);
         if (aux) (void)hipStreamDestroy((hipStream_t)aux);
@@ -868,14 +868,10 @@ static int ensure_scratch(SigScratch& sc, int dev, size_t n, bool with_sinv, siz
         }
         sc.chunk_cap = lanes;
     }
-    if (with_sinv && n > sc.sinv_cap) {
-        if (sc.sinv) BCC_HIP_TRY(hipFree(sc.sinv));
-        sc.sinv = nullptr;
-        sc.sinv_cap = 0;
-        size_t cap = std::max<size_t>(n, 1 << 12);
-        // per tuple: s^-1 (8 words), the loaded key's y (8 words) and its parse status (1 word)
-        BCC_HIP_TRY(hipMalloc(&sc.sinv, cap * PRE_WORDS * sizeof(u32)));
-        sc.sinv_cap = cap;
+    if (with_sinv) {
+        // per tuple: s^-1 (8 words), the loaded key's y (8 words) and its parse status (1 word);
+        // at least 4096 tuples
+        if (int e = sc.sinv.reserve(std::max<size_t>(n, 1 << 12) * PRE_WORDS * sizeof(u32))) return e;
     }
     *C = std::min(want, sc.chunk_cap);
     return 0;
@@ -891,7 +887,7 @@ int ecdsa_launch_pre(SigScratch& sc, const uint8_t* d_s, size_t n, void* stream)
     // K_inv: chunks of <= 16 tuples, but at least one wave per SIMD
     const size_t T = chain_threads(n, INV_PER_THREAD, cus);
     hipLaunchKernelGGL(batch_sinv_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, d_s, (u32*)sc.sinv, n, T);
+                       (hipStream_t)stream, d_s, (u32*)sc.sinv.p, n, T);
     BCC_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -930,18 +926,12 @@ static int launch_keyq(SigScratch& sc, int cus, const uint8_t* d_tag, const uint
                        u32* qtab, u32* state, const u32* emap, size_t ecount, hipStream_t st) {
     sc.q_split = 0;
     if (keyq_latency_mode(n, cus)) {
-        if (2 * n > sc.qtab2_cap) {
-            if (sc.qtab2) BCC_HIP_TRY(hipFree(sc.qtab2));
-            sc.qtab2 = nullptr;
-            sc.qtab2_cap = 0;
-            const size_t lanes = (2 * n + 255) & ~(size_t)255;
-            BCC_HIP_TRY(hipMalloc(&sc.qtab2, lanes * QTABLE_WORDS * sizeof(u32)));
-            sc.qtab2_cap = lanes;
-        }
+        const size_t lanes = (2 * n + 255) & ~(size_t)255;
+        if (int e = sc.qtab2.reserve(lanes * QTABLE_WORDS * sizeof(u32))) return e;
         const size_t groups = (2 * n + TLADDER_WG - 1) / TLADDER_WG;
         hipLaunchKernelGGL(twist_keyq2_kernel, dim3((unsigned)groups), dim3(TLADDER_WG),
                            (unsigned)keyq_lds(groups, cus, true), st, d_tag, d_x, d_y, d_r, d_s,
-                           (const u32*)sc.sinv, n, qtab, (u32*)sc.qtab2, state, emap, ecount);
+                           (const u32*)sc.sinv.p, n, qtab, (u32*)sc.qtab2.p, state, emap, ecount);
         return (int)hipGetLastError();
     }
     const size_t groups = (n + TLADDER_WG - 1) / TLADDER_WG;
@@ -955,12 +945,12 @@ static int launch_keyq(SigScratch& sc, int cus, const uint8_t* d_tag, const uint
             sc.ev_qa = e;
         }
         hipLaunchKernelGGL(twist_keyq_kernel, dim3((unsigned)(A / TLADDER_WG)), dim3(TLADDER_WG), 0, st,
-                           d_tag, d_x, d_y, d_r, d_s, (const u32*)sc.sinv, A, qtab, state, emap,
+                           d_tag, d_x, d_y, d_r, d_s, (const u32*)sc.sinv.p, A, qtab, state, emap,
                            ecount, (size_t)0);
         BCC_HIP_TRY(hipGetLastError());
         BCC_HIP_TRY(hipEventRecord((hipEvent_t)sc.ev_qa, st));
         hipLaunchKernelGGL(twist_keyq_kernel, dim3((unsigned)((n - A + TLADDER_WG - 1) / TLADDER_WG)),
-                           dim3(TLADDER_WG), 0, st, d_tag, d_x, d_y, d_r, d_s, (const u32*)sc.sinv,
+                           dim3(TLADDER_WG), 0, st, d_tag, d_x, d_y, d_r, d_s, (const u32*)sc.sinv.p,
                            n, qtab, state, emap, ecount, A);
         BCC_HIP_TRY(hipGetLastError());
         sc.q_split = A;
@@ -968,7 +958,7 @@ static int launch_keyq(SigScratch& sc, int cus, const uint8_t* d_tag, const uint
     }
     hipLaunchKernelGGL(twist_keyq_kernel, dim3((unsigned)groups), dim3(TLADDER_WG),
                        (unsigned)keyq_lds(groups, cus), st, d_tag, d_x, d_y, d_r, d_s,
-                       (const u32*)sc.sinv, n, qtab, state, emap, ecount, (size_t)0);
+                       (const u32*)sc.sinv.p, n, qtab, state, emap, ecount, (size_t)0);
     return (int)hipGetLastError();
 }
 
@@ -1046,7 +1036,7 @@ int ecdsa_launch_after_pre(SigScratch& sc, const uint8_t* d_tag, const uint8_t* 
     if (int e = device_tables(&dev, &gcomb, &cus)) return e;
     if (int e = ensure_scratch(sc, dev, n, true, &C)) return e;  // sized by ecdsa_launch_pre
     hipStream_t sm = (hipStream_t)stream;
-    u32* sinv = (u32*)sc.sinv;
+    u32* sinv = (u32*)sc.sinv.p;
     u32* qtab = (u32*)sc.chunk;
     u32* state = qtab + C * QTABLE_WORDS;
     const bool q_ahead = sc.q_ready == n && n <= C;
@@ -1162,33 +1152,16 @@ struct ThreadCtx {
     SigScratch sc;
     hipStream_t stream = nullptr;
     int dev = -1;
-    void* dbuf = nullptr;
-    size_t dcap = 0;
-    void* hbuf = nullptr;
-    size_t hcap = 0;
-    ~ThreadCtx() {
+    DeviceBuf dbuf;
+    PinnedBuf hbuf;
+    ~ThreadCtx() {  // (the buffers free themselves after this body, on dev)
         if (dev >= 0) (void)hipSetDevice(dev);
         if (stream) (void)hipStreamDestroy(stream);
-        if (dbuf) (void)hipFree(dbuf);
-        if (hbuf) (void)hipHostFree(hbuf);
     }
     int reserve(size_t bytes) { return reserve(bytes, bytes); }
     int reserve(size_t dbytes, size_t hbytes) {
-        if (dbytes > dcap) {
-            if (dbuf) BCC_HIP_TRY(hipFree(dbuf));
-            dbuf = nullptr;
-            dcap = 0;
-            BCC_HIP_TRY(hipMalloc(&dbuf, dbytes));
-            dcap = dbytes;
-        }
-        if (hbytes > hcap) {
-            if (hbuf) BCC_HIP_TRY(hipHostFree(hbuf));
-            hbuf = nullptr;
-            hcap = 0;
-            BCC_HIP_TRY(hipHostMalloc(&hbuf, hbytes, hipHostMallocDefault));
-            hcap = hbytes;
-        }
-        return 0;
+        if (int e = dbuf.reserve(dbytes)) return e;
+        return hbuf.reserve(hbytes);
     }
 };
 
@@ -1220,8 +1193,8 @@ int tuple_thread_buffers(int device, size_t dbytes, size_t hbytes, void** dbuf, 
     ThreadCtx* ctx = nullptr;
     if (int e = thread_ctx(device, &ctx)) return e;
     if (int e = ctx->reserve(dbytes, hbytes)) return e;
-    *dbuf = ctx->dbuf;
-    *hbuf = ctx->hbuf;
+    *dbuf = ctx->dbuf.p;
+    *hbuf = ctx->hbuf.p;
     *stream = ctx->stream;
     return 0;
 }
@@ -1269,8 +1242,6 @@ int mi_schnorr_verify_device(const uint8_t* d_sig64, const uint8_t* d_msg32,
     return schnorr_launch(*sc, d_sig64, d_msg32, d_xonly32, d_verdict, n, stream);
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // One device round of n BIP340 rows on the calling thread's context.
 static int schnorr_tuples_device(const uint8_t* sig64, const uint8_t* msg32, const uint8_t* xonly32,
                                  uint8_t* verdict, size_t n, int device) {
@@ -1280,8 +1251,8 @@ static int schnorr_tuples_device(const uint8_t* sig64, const uint8_t* msg32, con
     const size_t o_m = align256(64 * n), o_pk = o_m + align256(32 * n), o_v = o_pk + align256(32 * n);
     const size_t total = o_v + align256(n);
     if (int e = ctx->reserve(total)) return e;
-    uint8_t* h = (uint8_t*)ctx->hbuf;
-    uint8_t* d = (uint8_t*)ctx->dbuf;
+    uint8_t* h = ctx->hbuf.bytes();
+    uint8_t* d = ctx->dbuf.bytes();
     memcpy(h, sig64, 64 * n);
     memcpy(h + o_m, msg32, 32 * n);
     memcpy(h + o_pk, xonly32, 32 * n);
@@ -1339,8 +1310,8 @@ int mi_ecdsa_verify_tuples(const uint8_t* pub65, const uint8_t* msg32, const uin
     const size_t o_x = tagb, o_y = o_x + row, o_r = o_y + row, o_s = o_r + row, o_m = o_s + row,
                  o_v = o_m + row, total = o_v + tagb;
     if (int e = ctx->reserve(total)) return e;
-    uint8_t* h = (uint8_t*)ctx->hbuf;
-    uint8_t* d = (uint8_t*)ctx->dbuf;
+    uint8_t* h = ctx->hbuf.bytes();
+    uint8_t* d = ctx->dbuf.bytes();
     for (size_t i = 0; i < n; i++) {
         h[i] = pub65[65 * i];
         memcpy(h + o_x + 32 * i, pub65 + 65 * i + 1, 32);

@@ -2095,12 +2095,18 @@ size_t build_sighash_checks(const SighashCheck* checks, size_t n, SighashJobs& j
     return n;
 }
 
+// src's rows and jobs behind dst's, its records rebased to their place (pipeline.h PartBase /
+// rebase: the rule DeviceBatch::stage_parts applies to the parts of a device round).
 void append_round(SighashJobs& dst, TupleRows& drows, const SighashJobs& src,
                   const TupleRows& srows) {
-    const uint32_t row0 = (uint32_t)drows.size();
-    const uint32_t aux_blk0 = (uint32_t)(dst.aux.size() / 64), pre_blk0 = (uint32_t)(dst.pre.size() / 64);
-    const uint32_t aux_idx0 = (uint32_t)dst.aux_off.size();
+    const PartBase base = part_base(part_extent(&dst, drows));
     auto cat = [](auto& a, const auto& b) { a.insert(a.end(), b.begin(), b.end()); };
+    // b behind a, rebased by `by` (a base of one field, or all of them for a record)
+    auto cat_rebased = [](auto& a, const auto& b, const auto& by) {
+        const size_t at = a.size();
+        a.resize(at + b.size());
+        rebase_copy(a.data() + at, b.data(), b.size(), by);
+    };
     cat(drows.tag, srows.tag);
     cat(drows.x, srows.x);
     cat(drows.y, srows.y);
@@ -2109,47 +2115,20 @@ void append_round(SighashJobs& dst, TupleRows& drows, const SighashJobs& src,
     cat(drows.msg, srows.msg);
     cat(dst.aux, src.aux);
     cat(dst.pre, src.pre);
-    for (size_t i = 0; i < src.aux_off.size(); i++) {
-        dst.aux_off.push_back(src.aux_off[i] + aux_blk0);
-        dst.aux_nblk.push_back(src.aux_nblk[i]);
-    }
-    for (size_t i = 0; i < src.pre_off.size(); i++) {
-        dst.pre_off.push_back(src.pre_off[i] + pre_blk0);
-        dst.pre_nblk.push_back(src.pre_nblk[i]);
-        dst.pre_row.push_back(src.pre_row[i] + row0);
-    }
-    for (const auto& p : src.patches)
-        dst.patches.push_back(PatchRec{p.pre_byte + pre_blk0 * 64, p.aux + aux_idx0});
-    const uint32_t tpl0 = (uint32_t)dst.tpl.size(), code0 = (uint32_t)dst.code.size();
+    cat_rebased(dst.aux_off, src.aux_off, base.aux_blk);
+    cat(dst.aux_nblk, src.aux_nblk);
+    cat_rebased(dst.pre_off, src.pre_off, base.pre_blk);
+    cat(dst.pre_nblk, src.pre_nblk);
+    cat_rebased(dst.pre_row, src.pre_row, base.row);
+    cat_rebased(dst.patches, src.patches, base);
     cat(dst.tpl, src.tpl);
     cat(dst.code, src.code);
-    for (TplJob t : src.tjobs) {
-        t.tpl_off += tpl0;
-        t.code_off += code0;
-        t.row += row0;
-        dst.tjobs.push_back(t);
-    }
-    const uint32_t raw0 = (uint32_t)dst.txraw.size(), wtx0 = (uint32_t)dst.wtx.size();
-    const uint32_t win0 = dst.win_entries;
+    cat_rebased(dst.tjobs, src.tjobs, base);
     cat(dst.txraw, src.txraw);
-    for (WtxRec r : src.wtx) {
-        r.tx_off += raw0;
-        r.in_base += win0;
-        dst.wtx.push_back(r);
-    }
+    cat_rebased(dst.wtx, src.wtx, base);
     dst.win_entries += src.win_entries;
-    for (WinJob w : src.wjobs) {
-        w.tx += wtx0;
-        w.code_off += code0;
-        w.row += row0;
-        dst.wjobs.push_back(w);
-    }
-    for (LinJob l : src.ljobs) {
-        l.tx += wtx0;
-        l.code_off += code0;
-        l.row += row0;
-        dst.ljobs.push_back(l);
-    }
+    cat_rebased(dst.wjobs, src.wjobs, base);
+    cat_rebased(dst.ljobs, src.ljobs, base);
     dst.n_single_bug += src.n_single_bug;
     dst.n_win_single += src.n_win_single;
 }

@@ -37,7 +37,7 @@ struct SighashCheck {
 size_t build_sighash_checks(const SighashCheck* checks, size_t n, SighashJobs& jobs,
                             TupleRows& rows);
 
-// Appends src (jobs + rows) to dst, fixing offsets / indices.
+// Appends src (jobs + rows) to dst, its records rebased (pipeline.h PartBase / rebase).
 void append_round(SighashJobs& dst, TupleRows& dst_rows, const SighashJobs& src,
                   const TupleRows& src_rows);
 
@@ -62,8 +62,9 @@ int resilient_round(int dev, const SighashJobs* const* pj, const TupleRows* cons
 void taproot_release_thread_state();
 
 // The SigMsg digests of a part's device-built Taproot jobs computed on the host (taproot_host.cpp:
-// the CPU twin of sighash.hip taproot_tx_kernel + taproot_msg_kernel, part of the host evaluation
-// of a Taproot round; the CPU tests' stub device calls it too): msg + 32 row.
+// the CPU twin of sighash.hip taproot_tx_kernel + taproot_msg_kernel, which taproot_round.hip
+// launches; part of the host evaluation of a Taproot round; the CPU tests' stub device calls it
+// too): msg + 32 row.
 void taproot_dev_sigmsg_host(const TaprootTxJobs& jobs, uint8_t* msg);
 
 }  // namespace host

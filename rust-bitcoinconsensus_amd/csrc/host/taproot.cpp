@@ -7,7 +7,7 @@
 // sha_scriptpubkeys / sha_sequences / sha_outputs, :1366-1417 and :1455-1471, once per adjacent
 // run of items with the same tx; a check's sha_annex, :1889-1893, and sha_single_output,
 // :1556-1561).  Every SHA-256 compression and the BIP340 verification run on the GPU
-// (sighash.hip gpu_taproot_verify: aux hashes, digest patching, TapSighash from the tag
+// (taproot_round.hip gpu_taproot_verify over sighash.hip's kernels: aux hashes, digest patching, TapSighash from the tag
 // midstate, then the Schnorr kernels); a round of at most bcc_set_host_small_round() checks, and a
 // round the device could not deliver, is evaluated by the host instead (taproot_host.h).
 #include <chrono>

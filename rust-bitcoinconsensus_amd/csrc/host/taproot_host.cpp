@@ -1,7 +1,8 @@
 // The Taproot side on the host CPU (taproot_host.h).
 //
-// A Taproot device round (pipeline.h TaprootJobs: sighash.hip's aux / patch / TapSighash kernels,
-// taproot_tx_kernel + taproot_msg_kernel, then the BIP340 kernels) evaluated by host code:
+// A Taproot device round (pipeline.h TaprootJobs; taproot_round.hip launches sighash.hip's aux /
+// patch / TapSighash kernels, taproot_tx_kernel + taproot_msg_kernel, then the BIP340 kernels)
+// evaluated by host code:
 //   aux messages      single SHA-256 of the padded message
 //   host messages     aux digests patched in, SHA-256 from the TapSighash tag block
 //   device SigMsgs    the TtxRec / TapJob / ext records, assembled and hashed as the kernels do

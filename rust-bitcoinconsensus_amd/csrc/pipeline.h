@@ -6,6 +6,12 @@
 //   K_lin sha256d(raw-tx jobs)      other legacy hash types assembled from the raw tx (LinJob)
 //   K4 ecdsa_verify(tuples)         csrc/ecdsa_verify.hip
 // All four launch back-to-back on one stream with inputs resident in HBM.
+// Where things live: the job records and the rule that rebases them into a concatenation of parts
+// are below, next to each other; arena.h has the arena layout and the grow-only buffers;
+// sighash.hip holds the hash kernels (declared for their launchers in sighash_kernels.h);
+// device_batch.hip is the host side of DeviceBatch (staging, upload plan, launches, verdicts,
+// the page-locked pool, gpu_verify_* / gpu_staged_* / gpu_early_*); taproot_round.hip is the
+// Taproot device round (gpu_taproot_*); ecdsa_verify.hip the signature kernels and SigScratch.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -13,6 +19,8 @@
 #include <cstring>
 #include <vector>
 #include <functional>
+
+#include "arena.h"
 
 namespace bcc {
 
@@ -22,7 +30,7 @@ namespace bcc {
 // (DeviceBatch::stage_parts).  Blocks come from a process-wide pool in power-of-two classes and go
 // back to it, never to the runtime while the process runs (a hipHostFree would wait for the GPU in
 // the middle of a host pass), except through pinned_trim().  Without a device the pool hands out
-// ordinary memory (sighash.hip; the CPU test build's stub uses malloc).
+// ordinary memory (device_batch.hip; the CPU test build's stub uses malloc).
 void* pinned_alloc(size_t bytes);
 void pinned_free(void* p, size_t bytes) noexcept;
 void pinned_trim();
@@ -43,10 +51,59 @@ template <class T>
 using pinned_vector = std::vector<T, PinnedAlloc<T>>;
 using pinned_bytes = pinned_vector<uint8_t>;
 
+// A part's records (one host thread's SighashJobs + TupleRows, or TaprootJobs) index its own rows,
+// blobs and tables from zero.  Inside a concatenation of parts they are valid once the part's
+// bases are added: PartBase / TapBase hold them, and the rebase() overload below each record is the
+// one place that says which fields take which base.  The concatenations (host::append_round,
+// DeviceBatch::stage_parts, taproot_fill_part) all go through them.
+struct PartBase {   // ECDSA-era records
+    uint32_t row;      // tuple row
+    uint32_t aux_blk;  // 64-byte block in the aux blob
+    uint32_t pre_blk;  // 64-byte block in the preimage blob
+    uint32_t aux_idx;  // aux message index
+    uint32_t tpl;      // byte in the template blob
+    uint32_t code;     // byte in the code blob
+    uint32_t raw;      // byte in the raw tx blob
+    uint32_t wtx;      // WtxRec index
+    uint32_t win;      // device input table entry
+};
+struct TapBase {    // Taproot records
+    uint32_t row;      // BIP340 row
+    uint32_t aux_blk;  // 64-byte block in the aux blob
+    uint32_t msg_blk;  // 64-byte block in the SigMsg blob
+    uint32_t aux_idx;  // aux message index
+    uint32_t raw;      // byte in the raw tx blob
+    uint32_t ttx;      // TtxRec index
+    uint32_t ext;      // byte in the ext blob
+    uint32_t in;       // device input table entry
+};
+// dst[k] = src[k] + add: the offset arrays (aux_off + aux_blk, pre_off + pre_blk, pre_row + row,
+// msg_off + msg_blk, msg_row + row, hrow + row)
+inline void rebase_copy(uint32_t* dst, const uint32_t* src, size_t n, uint32_t add) {
+    for (size_t k = 0; k < n; k++) dst[k] = src[k] + add;
+}
+// dst[k] = src[k] rebased: an array of records
+template <class Rec, class Base>
+inline void rebase_copy(Rec* dst, const Rec* src, size_t n, const Base& b) {
+    for (size_t k = 0; k < n; k++) {
+        Rec r = src[k];
+        rebase(r, b);
+        dst[k] = r;
+    }
+}
+
 struct PatchRec {
     uint32_t pre_byte;  // absolute byte offset in the padded preimage buffer
     uint32_t aux;       // index of the aux message whose digest goes there
 };
+inline void rebase(PatchRec& p, const PartBase& b) {
+    p.pre_byte += b.pre_blk * 64;
+    p.aux += b.aux_idx;
+}
+inline void rebase(PatchRec& p, const TapBase& b) {  // Taproot: the patched blob is the SigMsg blob
+    p.pre_byte += b.msg_blk * 64;
+    p.aux += b.aux_idx;
+}
 
 // SHA-256 padding appended on the host so that the kernels only run whole 64-byte blocks.
 // `prefix` = bytes already absorbed into the starting midstate (a tagged hash's 64-byte tag
@@ -79,6 +136,11 @@ struct TplJob {
     uint32_t row;       // tuple row whose msg receives the sighash
     uint32_t nblk;      // padded message length in 64-byte blocks | TPL_MID when T carries midstates
 };
+inline void rebase(TplJob& t, const PartBase& b) {
+    t.tpl_off += b.tpl;
+    t.code_off += b.code;
+    t.row += b.row;
+}
 
 // Round 5: the template midstates.  Every legacy preimage of a tx begins with T's first
 // floor(pos / 64) blocks, so a long template is stored with the SHA-256 state after each of its
@@ -140,6 +202,10 @@ struct WtxRec {
     uint32_t in_base;  // first entry of this tx's inputs in the device input table
     uint32_t n_in;     // vin.size() as the host parsed it (table capacity) | WTX_TABLE_ONLY
 };
+inline void rebase(WtxRec& r, const PartBase& b) {
+    r.tx_off += b.raw;
+    r.in_base += b.win;
+}
 // A tx that only legacy jobs (LinJob) read: K_wtx writes its input table and hashes nothing (the
 // three BIP143 digests have no reader).  The first WinJob of the tx clears the flag.
 constexpr uint32_t WTX_TABLE_ONLY = 0x80000000u;
@@ -157,6 +223,11 @@ struct WinJob {
     uint32_t amount_lo, amount_hi;
 };
 static_assert(sizeof(WinJob) == 32, "WinJob: two 16-byte loads");
+inline void rebase(WinJob& w, const PartBase& b) {  // (a SINGLE job's trailing range is tx-relative)
+    w.tx += b.wtx;
+    w.code_off += b.code;
+    w.row += b.row;
+}
 BCC_PL_HD inline uint32_t win_single_trailer(const WinJob& j) {  // code blob offset of the two dwords
     return j.code_off + ((j.code_len + 3) & ~3u);
 }
@@ -177,6 +248,11 @@ struct LinJob {
     uint32_t out_off, out_len;
 };
 static_assert(sizeof(LinJob) == 32, "LinJob: two 16-byte loads");
+inline void rebase(LinJob& l, const PartBase& b) {  // (out_off is tx-relative)
+    l.tx += b.wtx;
+    l.code_off += b.code;
+    l.row += b.row;
+}
 
 struct SighashJobs {
     pinned_bytes aux, pre;                          // padded messages, back to back
@@ -379,6 +455,47 @@ struct TupleRows {
     }
 };
 
+// What one part adds to every array of a concatenation; the running sum over the parts before p
+// is where part p starts in each (at[p], with at[P] the totals).  size_t: the 4 GiB guards read
+// the totals before anything is narrowed to the records' 32 bits.
+struct PartExtent {
+    size_t row = 0, aux_bytes = 0, pre_bytes = 0, aux_idx = 0, pre_idx = 0, patch = 0, tpl = 0,
+           code = 0, tjob = 0, raw = 0, wtx = 0, wjob = 0, ljob = 0, win = 0, hrow = 0;
+    PartExtent& operator+=(const PartExtent& o) {
+        row += o.row; aux_bytes += o.aux_bytes; pre_bytes += o.pre_bytes; aux_idx += o.aux_idx;
+        pre_idx += o.pre_idx; patch += o.patch; tpl += o.tpl; code += o.code; tjob += o.tjob;
+        raw += o.raw; wtx += o.wtx; wjob += o.wjob; ljob += o.ljob; win += o.win; hrow += o.hrow;
+        return *this;
+    }
+};
+inline PartExtent part_extent(const SighashJobs* j, const TupleRows& rw) {  // j may be null: rows only
+    PartExtent e;
+    e.row = rw.size();
+    e.hrow = rw.hrow.size();
+    if (!j) return e;
+    e.aux_bytes = j->aux.size(); e.pre_bytes = j->pre.size();
+    e.aux_idx = j->aux_off.size(); e.pre_idx = j->pre_off.size(); e.patch = j->patches.size();
+    e.tpl = j->tpl.size(); e.code = j->code.size(); e.tjob = j->tjobs.size();
+    e.raw = j->txraw.size(); e.wtx = j->wtx.size(); e.wjob = j->wjobs.size();
+    e.ljob = j->ljobs.size(); e.win = j->win_entries;
+    return e;
+}
+// at[0..P]: the parts' starts and the totals (jobs may be null, or hold null entries)
+inline std::vector<PartExtent> part_starts(const SighashJobs* const* jobs, const TupleRows* const* rows,
+                                           size_t P) {
+    std::vector<PartExtent> at(P + 1);
+    for (size_t p = 0; p < P; p++) {
+        at[p + 1] = at[p];
+        at[p + 1] += part_extent(jobs ? jobs[p] : nullptr, *rows[p]);
+    }
+    return at;
+}
+inline PartBase part_base(const PartExtent& at) {
+    return PartBase{(uint32_t)at.row, (uint32_t)(at.aux_bytes / 64), (uint32_t)(at.pre_bytes / 64),
+                    (uint32_t)at.aux_idx, (uint32_t)at.tpl, (uint32_t)at.code, (uint32_t)at.raw,
+                    (uint32_t)at.wtx, (uint32_t)at.win};
+}
+
 // The device-built SigMsg path (sighash.hip taproot_tx_kernel / taproot_msg_kernel): per tx its
 // bytes without marker / flag / witnesses and the serialized outputs it spends (both 4-aligned in
 // txraw), per check a TapJob.
@@ -388,6 +505,11 @@ struct TtxRec {
     uint32_t in_base, n_in;   // input table entries [in_base, in_base + n_in)
     uint32_t pad[2];
 };
+inline void rebase(TtxRec& r, const TapBase& b) {
+    r.tx_off += b.raw;
+    r.sp_off += b.raw;
+    r.in_base += b.in;
+}
 struct TapJob {
     uint32_t ttx, nin, hash_type;
     uint32_t spend_type;  // (ext_flag << 1) | annex present (interpreter.cpp:1534)
@@ -396,6 +518,11 @@ struct TapJob {
     uint32_t codesep;     // BIP342 codesep_pos
     uint32_t flags;       // 1: BIP342 (tapleaf hash, key_version, codesep_pos follow)
 };
+inline void rebase(TapJob& j, const TapBase& b) {
+    j.ttx += b.ttx;
+    j.row += b.row;
+    j.ext_off += b.ext;
+}
 struct TaprootTxJobs {
     std::vector<uint8_t> txraw, ext;
     std::vector<TtxRec> ttx;
@@ -443,6 +570,69 @@ struct TaprootJobs {
     }
 };
 
+// The same for the Taproot parts: a part's extents, the parts' starts, a start's bases.
+struct TapExtent {
+    size_t row = 0, aux_bytes = 0, msg_bytes = 0, aux_idx = 0, msg_idx = 0, patch = 0, raw = 0,
+           ttx = 0, tjob = 0, ext = 0, in = 0;
+    TapExtent& operator+=(const TapExtent& o) {
+        row += o.row; aux_bytes += o.aux_bytes; msg_bytes += o.msg_bytes; aux_idx += o.aux_idx;
+        msg_idx += o.msg_idx; patch += o.patch; raw += o.raw; ttx += o.ttx; tjob += o.tjob;
+        ext += o.ext; in += o.in;
+        return *this;
+    }
+};
+inline TapExtent part_extent(const TaprootJobs& J) {
+    TapExtent e;
+    e.row = J.rows(); e.aux_bytes = J.aux.size(); e.msg_bytes = J.msg.size();
+    e.aux_idx = J.aux_off.size(); e.msg_idx = J.msg_off.size(); e.patch = J.patches.size();
+    e.raw = J.dev.txraw.size(); e.ttx = J.dev.ttx.size(); e.tjob = J.dev.jobs.size();
+    e.ext = J.dev.ext.size(); e.in = J.dev.in_entries;
+    return e;
+}
+inline std::vector<TapExtent> part_starts(const TaprootJobs* const* parts, size_t P) {
+    std::vector<TapExtent> at(P + 1);
+    for (size_t p = 0; p < P; p++) {
+        at[p + 1] = at[p];
+        at[p + 1] += part_extent(*parts[p]);
+    }
+    return at;
+}
+inline TapBase part_base(const TapExtent& at) {
+    return TapBase{(uint32_t)at.row, (uint32_t)(at.aux_bytes / 64), (uint32_t)(at.msg_bytes / 64),
+                   (uint32_t)at.aux_idx, (uint32_t)at.raw, (uint32_t)at.ttx, (uint32_t)at.ext,
+                   (uint32_t)at.in};
+}
+// The arrays of a concatenation of Taproot parts, wherever they live (the pinned image of a device
+// round, or plain vectors), and the one function that writes part J into them at its start `at`.
+struct TapImage {
+    uint8_t *sig64, *pk32, *aux, *msg;
+    uint32_t *aux_off, *aux_nblk, *msg_off, *msg_nblk, *msg_row;
+    PatchRec* patches;
+    uint8_t *txraw, *ext;
+    TtxRec* ttx;
+    TapJob* jobs;
+};
+inline void taproot_fill_part(const TapImage& im, const TaprootJobs& J, const TapExtent& at) {
+    const TapBase b = part_base(at);
+    auto cp = [](void* dst, const void* src, size_t len) {
+        if (len) memcpy(dst, src, len);
+    };
+    cp(im.sig64 + 64 * at.row, J.sig64.data(), 64 * J.rows());
+    cp(im.pk32 + 32 * at.row, J.pk32.data(), 32 * J.rows());
+    cp(im.aux + at.aux_bytes, J.aux.data(), J.aux.size());
+    cp(im.msg + at.msg_bytes, J.msg.data(), J.msg.size());
+    rebase_copy(im.aux_off + at.aux_idx, J.aux_off.data(), J.aux_off.size(), b.aux_blk);
+    cp(im.aux_nblk + at.aux_idx, J.aux_nblk.data(), 4 * J.aux_nblk.size());
+    rebase_copy(im.msg_off + at.msg_idx, J.msg_off.data(), J.msg_off.size(), b.msg_blk);
+    rebase_copy(im.msg_row + at.msg_idx, J.msg_row.data(), J.msg_row.size(), b.row);
+    cp(im.msg_nblk + at.msg_idx, J.msg_nblk.data(), 4 * J.msg_nblk.size());
+    rebase_copy(im.patches + at.patch, J.patches.data(), J.patches.size(), b);
+    cp(im.txraw + at.raw, J.dev.txraw.data(), J.dev.txraw.size());
+    cp(im.ext + at.ext, J.dev.ext.data(), J.dev.ext.size());
+    rebase_copy(im.ttx + at.ttx, J.dev.ttx.data(), J.dev.ttx.size(), b);
+    rebase_copy(im.jobs + at.tjob, J.dev.jobs.data(), J.dev.jobs.size(), b);
+}
+
 // SHA256(tag) || SHA256(tag) compressed from the IV: the starting midstate of the TapSighash
 // tagged hash (host/taproot.cpp computes it once).
 void tapsighash_midstate(uint32_t out[8]);
@@ -484,14 +674,12 @@ int gpu_taproot_end_extra(int device, int slot, uint8_t* verdict, uint8_t* msg32
 // that share a scratch must be ordered (one stream).
 struct SigScratch {
     int dev = -1;
-    void* sinv = nullptr;
-    size_t sinv_cap = 0;   // tuples
+    DeviceBuf sinv;        // s^-1 rows (PRE_WORDS words per tuple)
     void* chunk = nullptr;
     size_t chunk_cap = 0;  // lanes
     size_t chunk_short = 0;  // a chunk request the device could not hold (served by chunk_cap)
     size_t q_ready = 0;    // tuples whose Q ladder ran ahead (ecdsa_launch_q)
-    void* qtab2 = nullptr;  // the Q tables of K_keyq's latency mode (two lanes per tuple)
-    size_t qtab2_cap = 0;   // lanes
+    DeviceBuf qtab2;        // the Q tables of K_keyq's latency mode (two lanes per tuple)
     // Round 6, the residency tail: K_keyq of a launch that is not a whole number of residency
     // rounds runs as two launches, [0, q_split) and [q_split, q_ready); ev_qa is recorded after
     // the first, so the G ladder of those lanes can fill the idle slots of the second's last
@@ -655,7 +843,7 @@ private:
     bool up_msg_one_ = false;      // the msg rows are set to ONE with the upload
     // per-shard row pre-upload (pre_arm / pre_upload): shard t's tag | x | r | s at pre_buf_[t]
     static constexpr unsigned PRE_MAX_SHARDS = 64;
-    std::vector<uint8_t*> pre_buf_;
+    std::vector<DeviceBuf> pre_buf_;
     size_t pre_cap_ = 0;               // rows per shard buffer
     std::vector<size_t> pre_rows_;     // rows sent per shard (SIZE_MAX: none)
     unsigned pre_P_ = 0;
@@ -670,9 +858,8 @@ private:
     int put_late(struct ihipStream_t* st, const LateMsgFill* late);  // late rows -> d_m (K_late)
     std::vector<uint32_t> late_rows_;
     std::vector<uint8_t> late_digs_;
-    void* late_host_ = nullptr;  // pinned: rows then digests
-    uint8_t* late_dev_ = nullptr;
-    size_t late_cap_ = 0;        // entries of late_host_ / late_dev_
+    PinnedBuf late_host_;        // rows then digests
+    DeviceBuf late_dev_;
     bool kh_done_ = false;  // run_stages ran K_h160 already (ahead of the ladder, verdict_and)
     int dev_;
     void* own_stream_ = nullptr;   // hipStream_t, created on first use
@@ -685,16 +872,12 @@ private:
     void* ev_block_ = nullptr;     // hipEvent_t (blocking sync): host waits sleep, not spin
     int wait(void* stream);
     SigScratch scratch_;
-    void* arena_ = nullptr;
-    size_t cap_ = 0;
-    void* host_image_ = nullptr;  // pinned host image of the arena (staging)
-    size_t host_cap_ = 0;
-    void* vbuf_ = nullptr;        // pinned verdict buffer (fetch_verdicts)
-    size_t vcap_ = 0;
+    DeviceBuf arena_;
+    PinnedBuf host_image_;        // pinned host image of the arena (staging)
+    PinnedBuf vbuf_;              // pinned verdict buffer (fetch_verdicts)
     // Round 5: the verdicts reach vbuf_ through a kernel queued behind the round's last kernel
     // (queue_verdicts), not a copy-engine D2H issued at fetch time, which waited in the one copy
-    // queue behind the next pipelined round's upload
-    void* vbuf_dev_ = nullptr;    // vbuf_ as the device addresses it
+    // queue behind the next pipelined round's upload (vbuf_.dev: vbuf_ as the device addresses it)
     bool v_queued_ = false;       // the current run's verdicts are on their way to vbuf_
     int ensure_vbuf();            // vbuf_ for n_rows_ (stage time: run() allocates nothing)
     int queue_verdicts(struct ihipStream_t* st);
@@ -741,10 +924,8 @@ private:
     bool early_pending_ = false;    // ev_early_ recorded and maybe not reached yet
     size_t early_n_ = 0;            // rows of the current early set (0: none)
     SigScratch early_scratch_;
-    void* early_arena_ = nullptr;   // tag | x | y | r | s rows of the early set
-    size_t early_cap_ = 0;
-    void* early_host_ = nullptr;    // pinned image of early_arena_
-    size_t early_host_cap_ = 0;
+    DeviceBuf early_arena_;         // tag | x | y | r | s rows of the early set
+    PinnedBuf early_host_;          // pinned image of early_arena_
     void* early_sig_stream_ = nullptr;  // hipStream_t: the early sighash jobs
     void* ev_early_up_ = nullptr;       // hipEvent_t: the early image uploaded
     void* ev_early_sig_ = nullptr;      // hipEvent_t: the early sighashes done
@@ -772,7 +953,7 @@ void set_direct_upload(bool on);
 bool direct_upload();
 
 // Free the calling thread's cached device state: the verify_batch / Taproot device batches and
-// contexts (sighash.hip) and the tuple-path contexts (ecdsa_verify.hip).
+// contexts (device_batch.hip, taproot_round.hip) and the tuple-path contexts (ecdsa_verify.hip).
 void release_device_thread_state();
 void release_tuple_thread_state();
 

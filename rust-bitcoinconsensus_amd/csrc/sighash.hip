@@ -4,31 +4,16 @@
 //   K3 sha256d_msgs   preimages -> sighash, written straight into the ECDSA tuple msg rows
 // Integer-ALU bound (~2k VALU ops per 64-byte block); HBM traffic per launch is reported by
 // bench.py as the algorithmic bytes (message bytes in + 32 B out per message).
-#include <atomic>
-#include <chrono>
-#include <cstdlib>
-#include <memory>
-#include <mutex>
-#include <new>
-#include <thread>
-#include <vector>
-#include <cstring>
-#include <cstdio>
-
+// This file holds the kernels only: device_batch.hip (the ECDSA-era rounds) and taproot_round.hip
+// (the BIP341 rounds) stage their inputs and launch them through sighash_kernels.h.
 #include "gpu_common.h"
 #include "pipeline.h"
 #include "sha256_device.h"
-#include "host/hashes.h"
-#include "host/team.h"
+#include "sighash_kernels.h"
 
 namespace bcc {
 
 __device__ __forceinline__ uint32_t bswap_u32(uint32_t x) { return __builtin_bswap32(x); }
-
-// A starting SHA-256 state passed by value (kernel argument: lands in SGPRs).
-struct ShaMid {
-    uint32_t s[8];
-};
 
 // Each lane streams its own message 64 bytes at a time (four 16-byte loads; messages are
 // 64-byte aligned so every load is a full aligned 16-byte access).  kDouble: SHA-256d (the
@@ -278,7 +263,6 @@ __device__ __forceinline__ void sha256d_tpl_lane(const uint8_t* __restrict__ tpl
 // own LDS slot (96 bytes, + 4 so that lane slots start on different banks), so byte positions can
 // be dynamic without scratch memory; the compression reads the block back as 16 words.
 constexpr int XS_SLOT = 100;   // bytes per lane: block[64] | state[32] | pad
-constexpr int XS_WG = 64;      // lanes per workgroup of the extraction kernels
 
 __device__ __noinline__ void xs_compress(uint8_t* slot) {
     const uint32_t* b = reinterpret_cast<const uint32_t*>(slot);
@@ -985,750 +969,8 @@ __global__ __launch_bounds__(256) void patch_digests_kernel(uint8_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-DeviceBatch::DeviceBatch(int device) : dev_(device) {}
-
-DeviceBatch::~DeviceBatch() {
-    (void)hipSetDevice(dev_);
-    if (own_stream_) (void)hipStreamDestroy((hipStream_t)own_stream_);
-    if (side_stream_) (void)hipStreamDestroy((hipStream_t)side_stream_);
-    if (ev_fork_) (void)hipEventDestroy((hipEvent_t)ev_fork_);
-    if (ev_join_) (void)hipEventDestroy((hipEvent_t)ev_join_);
-    if (ev_up_) (void)hipEventDestroy((hipEvent_t)ev_up_);
-    if (ev_rows_up_) (void)hipEventDestroy((hipEvent_t)ev_rows_up_);
-    if (pre_stream_) {
-        (void)hipStreamSynchronize((hipStream_t)pre_stream_);
-        (void)hipStreamDestroy((hipStream_t)pre_stream_);
-    }
-    if (ev_pre_) (void)hipEventDestroy((hipEvent_t)ev_pre_);
-    for (uint8_t* b : pre_buf_)
-        if (b) (void)hipFree(b);
-    if (ev_block_) (void)hipEventDestroy((hipEvent_t)ev_block_);
-    if (arena_) (void)hipFree(arena_);
-    if (host_image_) (void)hipHostFree(host_image_);
-    if (vbuf_) (void)hipHostFree(vbuf_);
-    if (late_host_) (void)hipHostFree(late_host_);
-    if (late_dev_) (void)hipFree(late_dev_);
-    if (early_stream_) {
-        (void)hipStreamSynchronize((hipStream_t)early_stream_);
-        (void)hipStreamDestroy((hipStream_t)early_stream_);
-    }
-    if (early_sig_stream_) {
-        (void)hipStreamSynchronize((hipStream_t)early_sig_stream_);
-        (void)hipStreamDestroy((hipStream_t)early_sig_stream_);
-    }
-    if (ev_early_) (void)hipEventDestroy((hipEvent_t)ev_early_);
-    if (ev_early_up_) (void)hipEventDestroy((hipEvent_t)ev_early_up_);
-    if (ev_early_sig_) (void)hipEventDestroy((hipEvent_t)ev_early_sig_);
-    if (early_arena_) (void)hipFree(early_arena_);
-    if (early_host_) (void)hipHostFree(early_host_);
-}
-
-// Early Q halves: the rows go up on the batch's early stream, then K_inv and K_keyq over them into
-// early_scratch_ (their own scratch: the round's K_keyq copies from it).  The previous set's work
-// (a call whose rounds never needed it) is waited for before its image and scratch are reused.
-int DeviceBatch::early_launch(const TupleRows* const* Rw, size_t P, const SighashJobs* const* Jp) {
-    early_n_ = 0;
-    early_msgs_ = false;
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    if (!early_stream_) {
-        hipStream_t s = nullptr, s2 = nullptr;
-        hipEvent_t e = nullptr, e2 = nullptr, e3 = nullptr;
-        BCC_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        BCC_HIP_TRY(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-        BCC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        BCC_HIP_TRY(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-        BCC_HIP_TRY(hipEventCreateWithFlags(&e3, hipEventDisableTiming));
-        early_stream_ = s;
-        early_sig_stream_ = s2;
-        ev_early_ = e;
-        ev_early_up_ = e2;
-        ev_early_sig_ = e3;
-    }
-    hipStream_t es = (hipStream_t)early_stream_, ss = (hipStream_t)early_sig_stream_;
-    if (early_pending_) {
-        BCC_HIP_TRY(hipStreamSynchronize(es));
-        BCC_HIP_TRY(hipStreamSynchronize(ss));
-        early_pending_ = false;
-    }
-    std::vector<size_t> row0(P + 1, 0), tpl0(P + 1, 0), code0(P + 1, 0), tj0(P + 1, 0);
-    bool need_y = false;
-    for (size_t p = 0; p < P; p++) {
-        row0[p + 1] = row0[p] + Rw[p]->size();
-        need_y |= !Rw[p]->y_unused && Rw[p]->size() != 0;
-        const SighashJobs* j = Jp ? Jp[p] : nullptr;
-        tpl0[p + 1] = tpl0[p] + (j ? j->tpl.size() : 0);
-        code0[p + 1] = code0[p] + (j ? j->code.size() : 0);
-        tj0[p + 1] = tj0[p] + (j ? j->tjobs.size() : 0);
-    }
-    const size_t R = row0[P], NT = tj0[P];
-    if (R == 0) return 0;
-    if (tpl0[P] >= ((size_t)1 << 32) || code0[P] >= ((size_t)1 << 32)) return (int)hipErrorInvalidValue;
-    // tag | x | y | r | s | TPL | CODE | TJOB (uploaded) | MSG (device-written), each 256-aligned
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_tag = 0, o_x = al(R), o_y = o_x + al(32 * R), o_r = o_y + al(32 * R),
-                 o_s = o_r + al(32 * R), o_tpl = o_s + al(32 * R), o_code = o_tpl + al(tpl0[P] + 64),
-                 o_tj = o_code + al(code0[P] + 64), o_msg = o_tj + al(sizeof(TplJob) * NT),
-                 upload = NT ? o_msg : o_tpl, total = o_msg + al(NT ? 32 * R : 0);
-    if (total > early_cap_) {
-        if (early_arena_) BCC_HIP_TRY(hipFree(early_arena_));
-        early_arena_ = nullptr;
-        early_cap_ = 0;
-        BCC_HIP_TRY(hipMalloc(&early_arena_, total));
-        early_cap_ = total;
-    }
-    if (upload > early_host_cap_) {
-        if (early_host_) BCC_HIP_TRY(hipHostFree(early_host_));
-        early_host_ = nullptr;
-        early_host_cap_ = 0;
-        BCC_HIP_TRY(hipHostMalloc(&early_host_, upload, hipHostMallocDefault));
-        early_host_cap_ = upload;
-    }
-    uint8_t* h = (uint8_t*)early_host_;
-    auto fill = [&](size_t p) {
-        const TupleRows& rw = *Rw[p];
-        const size_t r0 = row0[p], nr = rw.size();
-        if (!nr) return;
-        memcpy(h + o_tag + r0, rw.tag.data(), nr);
-        memcpy(h + o_x + 32 * r0, rw.x.data(), 32 * nr);
-        if (need_y) rw.copy_y(h + o_y + 32 * r0, 0, nr);
-        memcpy(h + o_r + 32 * r0, rw.r.data(), 32 * nr);
-        memcpy(h + o_s + 32 * r0, rw.s.data(), 32 * nr);
-        if (!NT || !Jp || !Jp[p]) return;
-        const SighashJobs& j = *Jp[p];
-        if (!j.tpl.empty()) memcpy(h + o_tpl + tpl0[p], j.tpl.data(), j.tpl.size());
-        if (!j.code.empty()) memcpy(h + o_code + code0[p], j.code.data(), j.code.size());
-        TplJob* tj = (TplJob*)(h + o_tj) + tj0[p];
-        for (size_t k = 0; k < j.tjobs.size(); k++) {
-            TplJob t = j.tjobs[k];
-            t.tpl_off += (uint32_t)tpl0[p];
-            t.code_off += (uint32_t)code0[p];
-            t.row += (uint32_t)r0;
-            t.nblk &= ~TPL_EARLY;
-            tj[k] = t;
-        }
-    };
-    if (NT) {  // the blobs' tails the lanes may read past (dword loads)
-        memset(h + o_tpl + tpl0[P], 0, 64);
-        memset(h + o_code + code0[P], 0, 64);
-    }
-    if (P > 1 && R >= 4096) host::run_team((unsigned)std::min<size_t>(P, 16), [&](unsigned t) {
-        for (size_t p = t; p < P; p += std::min<size_t>(P, 16)) fill(p);
-    });
-    else
-        for (size_t p = 0; p < P; p++) fill(p);
-    uint8_t* a = (uint8_t*)early_arena_;
-    BCC_HIP_TRY(hipMemcpyAsync(a, h, need_y ? upload : o_y, hipMemcpyHostToDevice, es));
-    if (!need_y) BCC_HIP_TRY(hipMemcpyAsync(a + o_r, h + o_r, upload - o_r, hipMemcpyHostToDevice, es));
-    if (NT) {  // the early sighashes on their own stream, beside K_inv / K_keyq
-        BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_early_up_, es));
-        BCC_HIP_TRY(hipStreamWaitEvent(ss, (hipEvent_t)ev_early_up_, 0));
-        hipLaunchKernelGGL(sighash_front_kernel, dim3((unsigned)((NT + XS_WG - 1) / XS_WG)), dim3(XS_WG), 0,
-                           ss, nullptr, nullptr, 0u, nullptr, nullptr, a + o_tpl, a + o_code,
-                           (const TplJob*)(a + o_tj), (uint32_t)NT, nullptr, nullptr, nullptr, 0u,
-                           nullptr, a + o_msg);
-        BCC_HIP_TRY(hipGetLastError());
-        BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_early_sig_, ss));
-        early_msg_ = a + o_msg;
-    }
-    const uint8_t *dt = a + o_tag, *dx = a + o_x, *dy = a + o_y, *dr = a + o_r, *ds = a + o_s;
-    if (int e = ecdsa_launch_pre(early_scratch_, ds, R, es)) return e;
-    if (int e = ecdsa_launch_q(early_scratch_, dt, dx, dy, dr, ds, R, es)) return e;
-    const bool launched = early_scratch_.q_ready == R;
-    early_scratch_.q_ready = 0;
-    BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_early_, es));
-    early_pending_ = true;
-    if (launched) {
-        early_n_ = R;
-        early_msgs_ = NT != 0;
-    }
-    return 0;
-}
-
-void DeviceBatch::early_reset() {
-    early_n_ = 0;
-    early_msgs_ = false;
-}
-
-void* DeviceBatch::pick(void* stream) {
-    if (!stream) {
-        if (!own_stream_) {
-            hipStream_t s = nullptr;
-            if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-            own_stream_ = s;
-        }
-        stream = own_stream_;
-    }
-    last_stream_ = stream;
-    return stream;
-}
-
-// Host waits on a blocking-sync event: the waiting thread sleeps instead of spinning on a core
-// (the host pass may be running beside it on the same CPU share).
-int DeviceBatch::wait(void* stream) {
-    if (!ev_block_) {
-        hipEvent_t e = nullptr;
-        BCC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventBlockingSync | hipEventDisableTiming));
-        ev_block_ = e;
-    }
-    BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_block_, (hipStream_t)stream));
-    BCC_HIP_TRY(hipEventSynchronize((hipEvent_t)ev_block_));
-    return 0;
-}
-
-int DeviceBatch::sync() {
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    if (last_stream_) return wait(last_stream_);
-    return 0;
-}
-
-thread_local unsigned tl_stage_threads = 0;
-void set_stage_threads(unsigned n) { tl_stage_threads = n; }
-
-static std::atomic<bool> g_direct_upload{[] {
-    const char* e = getenv("BCC_DIRECT_UPLOAD");
-    return !(e && atoi(e) == 0);
-}()};
-void set_direct_upload(bool on) { g_direct_upload.store(on, std::memory_order_relaxed); }
-bool direct_upload() { return g_direct_upload.load(std::memory_order_relaxed); }
-
-// The page-locked pool (pipeline.h, pinned_alloc): free lists per power-of-two class from 4 KiB,
-// under one mutex; the pool object is never destroyed (thread-exit destructors of cached
-// TupleRows may return blocks after static destruction began).  A block the runtime refused to
-// pin (no device) is ordinary memory, remembered so that it is freed as such.
-namespace {
-struct PinPool {
-    std::mutex mu;
-    std::vector<void*> free_[64];
-    std::vector<void*> pageable;
-};
-PinPool& pin_pool() {
-    static PinPool* p = new PinPool;
-    return *p;
-}
-int pin_class(size_t bytes) {
-    int k = 12;
-    while (((size_t)1 << k) < bytes) k++;
-    return k;
-}
-}  // namespace
-void* pinned_alloc(size_t bytes) {
-    const int k = pin_class(bytes ? bytes : 1);
-    PinPool& pp = pin_pool();
-    {
-        std::lock_guard<std::mutex> g(pp.mu);
-        if (!pp.free_[k].empty()) {
-            void* q = pp.free_[k].back();
-            pp.free_[k].pop_back();
-            return q;
-        }
-    }
-    void* q = nullptr;
-    if (hipHostMalloc(&q, (size_t)1 << k, hipHostMallocDefault) == hipSuccess && q) return q;
-    (void)hipGetLastError();
-    q = aligned_alloc(4096, (size_t)1 << k);
-    if (!q) throw std::bad_alloc();
-    std::lock_guard<std::mutex> g(pp.mu);
-    pp.pageable.push_back(q);
-    return q;
-}
-void pinned_free(void* q, size_t bytes) noexcept {
-    if (!q) return;
-    PinPool& pp = pin_pool();
-    std::lock_guard<std::mutex> g(pp.mu);
-    try {
-        pp.free_[pin_class(bytes ? bytes : 1)].push_back(q);
-    } catch (...) {  // out of memory for the list itself: keep the block
-    }
-}
-void pinned_trim() {
-    PinPool& pp = pin_pool();
-    std::lock_guard<std::mutex> g(pp.mu);
-    for (auto& l : pp.free_) {
-        for (void* q : l) {
-            auto it = std::find(pp.pageable.begin(), pp.pageable.end(), q);
-            if (it != pp.pageable.end()) {
-                pp.pageable.erase(it);
-                free(q);
-            } else {
-                (void)hipHostFree(q);
-            }
-        }
-        l.clear();
-        l.shrink_to_fit();
-    }
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int DeviceBatch::stage(const SighashJobs& j, const TupleRows& rows) {
-    const SighashJobs* jp = &j;
-    const TupleRows* rp = &rows;
-    return stage_parts(&jp, &rp, 1);
-}
-
-// The parts (one per host interpreter thread) are concatenated in order straight into a pinned
-// host image of the device arena, each part by its own thread with its index fix-ups (the
-// append_round rules), then the image goes to HBM in one DMA copy: no merged host copy of the
-// jobs and no pageable-memory staging.
-int DeviceBatch::stage_parts(const SighashJobs* const* J, const TupleRows* const* Rw, size_t P,
-                             bool direct_arg) {
-    if (int e = sync()) return e;  // the previous run may still read the arena / the image
-    n_der_ = 0;
-    std::vector<size_t> row0(P + 1, 0), auxb0(P + 1, 0), preb0(P + 1, 0), auxi0(P + 1, 0),
-        prei0(P + 1, 0), pat0(P + 1, 0), tpl0(P + 1, 0), code0(P + 1, 0), tj0(P + 1, 0),
-        raw0(P + 1, 0), wtx0(P + 1, 0), wj0(P + 1, 0), win0(P + 1, 0), h0(P + 1, 0), lj0(P + 1, 0);
-    for (size_t p = 0; p < P; p++) {
-        row0[p + 1] = row0[p] + Rw[p]->size();
-        auxb0[p + 1] = auxb0[p] + J[p]->aux.size();
-        preb0[p + 1] = preb0[p] + J[p]->pre.size();
-        auxi0[p + 1] = auxi0[p] + J[p]->aux_off.size();
-        prei0[p + 1] = prei0[p] + J[p]->pre_off.size();
-        pat0[p + 1] = pat0[p] + J[p]->patches.size();
-        tpl0[p + 1] = tpl0[p] + J[p]->tpl.size();
-        code0[p + 1] = code0[p] + J[p]->code.size();
-        tj0[p + 1] = tj0[p] + J[p]->tjobs.size();
-        raw0[p + 1] = raw0[p] + J[p]->txraw.size();
-        wtx0[p + 1] = wtx0[p] + J[p]->wtx.size();
-        wj0[p + 1] = wj0[p] + J[p]->wjobs.size();
-        lj0[p + 1] = lj0[p] + J[p]->ljobs.size();
-        win0[p + 1] = win0[p] + J[p]->win_entries;
-        h0[p + 1] = h0[p] + Rw[p]->hrow.size();
-    }
-    // per part, summed by the fill below (one pass over the records, in parallel): the template
-    // jobs' blocks and the BIP143 inputs' algorithmic bytes (bcc_workload_sighash_bytes)
-    std::vector<size_t> part_tjblk(P, 0), part_wbytes(P, 0);
-    const size_t LIM = (size_t)1 << 32;
-    if (auxb0[P] >= LIM || preb0[P] >= LIM || tpl0[P] >= LIM || code0[P] >= LIM ||
-        raw0[P] >= LIM || row0[P] >= LIM || win0[P] >= LIM / 2) {
-        // the job records (PatchRec, TplJob, WtxRec, WinJob, offsets) are 32-bit: refuse, never wrap
-        fprintf(stderr, "[bcc] DeviceBatch::stage_parts: a job blob exceeds 4 GiB; split the round\n");
-        return (int)hipErrorInvalidValue;
-    }
-    n_rows_ = row0[P];
-    n_pre_ = prei0[P];
-    n_aux_ = auxi0[P];
-    n_patch_ = pat0[P];
-    pre_blocks_ = preb0[P] / 64;
-    aux_blocks_ = auxb0[P] / 64;
-    n_tjob_ = tj0[P];
-
-    n_wtx_ = wtx0[P];
-    n_wjob_ = wj0[P];
-    n_ljob_ = lj0[P];
-    n_win_ = win0[P];
-    n_hash_ = h0[P];
-    const size_t R = n_rows_;
-    // regions filled from the host image first (one copy), device-written ones after them
-    // Y and M go up only when some part needs them (TupleRows::y_unused / msg_one)
-    enum { TAG, X, RR, S, EMAP, MMAP, AUX, PRE, AUX_OFF, AUX_NBLK, PRE_OFF, PRE_NBLK, PRE_ROW, PATCH,
-           TPL, CODE, TJOB, TXRAW, WTX, WJOB, LJOB, HROW, HPROG, ZEROS, UPLOADED, Y = UPLOADED, M, V, AUXD, INTAB, TXD,
-           NB };
-    bool need_y = false, need_m = false, need_e = false, need_mm = false;
-    for (size_t p = 0; p < P; p++) {
-        need_y |= !Rw[p]->y_unused && Rw[p]->size() != 0;
-        need_m |= !Rw[p]->msg_one && Rw[p]->size() != 0;
-        need_e |= !Rw[p]->emap.empty();
-        need_mm |= !Rw[p]->mmap.empty();
-    }
-    need_e = need_e && early_n_ != 0;  // early twins exist for this batch's call (early_launch)
-    // early sighashes (TPL_EARLY jobs) only with live early digests; else the jobs run as usual
-    need_mm = need_mm && early_n_ != 0 && early_msgs_;
-    size_t sizes[NB] = {};
-    sizes[TAG] = R; sizes[X] = sizes[Y] = sizes[RR] = sizes[S] = sizes[M] = 32 * R;
-    sizes[EMAP] = need_e ? 4 * R : 0;
-    sizes[MMAP] = need_mm ? 4 * R : 0;
-    sizes[AUX] = auxb0[P]; sizes[PRE] = preb0[P];
-    sizes[AUX_OFF] = sizes[AUX_NBLK] = 4 * n_aux_;
-    sizes[PRE_OFF] = sizes[PRE_NBLK] = sizes[PRE_ROW] = 4 * n_pre_;
-    sizes[PATCH] = sizeof(PatchRec) * n_patch_;
-    sizes[TPL] = tpl0[P]; sizes[CODE] = code0[P]; sizes[TJOB] = sizeof(TplJob) * n_tjob_;
-    sizes[TXRAW] = raw0[P]; sizes[WTX] = sizeof(WtxRec) * n_wtx_; sizes[WJOB] = sizeof(WinJob) * n_wjob_;
-    sizes[LJOB] = sizeof(LinJob) * n_ljob_;
-    sizes[HROW] = 4 * n_hash_; sizes[HPROG] = 20 * n_hash_;
-    sizes[ZEROS] = 64;
-    sizes[V] = R; sizes[AUXD] = 32 * n_aux_; sizes[INTAB] = 8 * n_win_; sizes[TXD] = 96 * n_wtx_;
-    size_t off[NB], total = 0;
-    for (int i = 0; i < NB; i++) {
-        off[i] = total;
-        total += align256(sizes[i]);
-    }
-    const size_t upload = off[UPLOADED], upload_ym = off[V];  // the image holds Y and M too
-    if (total > cap_) {
-        if (arena_) BCC_HIP_TRY(hipFree(arena_));
-        arena_ = nullptr;
-        cap_ = 0;
-        BCC_HIP_TRY(hipMalloc(&arena_, total));
-        cap_ = total;
-    }
-    if (upload_ym > host_cap_) {
-        if (host_image_) BCC_HIP_TRY(hipHostFree(host_image_));
-        host_image_ = nullptr;
-        host_cap_ = 0;
-        BCC_HIP_TRY(hipHostMalloc(&host_image_, upload_ym, hipHostMallocDefault));
-        host_cap_ = upload_ym;
-    }
-    uint8_t* a = (uint8_t*)arena_;
-    d_tag = a + off[TAG]; d_x = a + off[X]; d_y = a + off[Y]; d_r = a + off[RR]; d_s = a + off[S];
-    d_m = a + off[M]; d_v = a + off[V]; d_aux_ = a + off[AUX]; d_pre_ = a + off[PRE];
-    d_auxd_ = a + off[AUXD];
-    d_aux_off_ = (uint32_t*)(a + off[AUX_OFF]); d_aux_nblk_ = (uint32_t*)(a + off[AUX_NBLK]);
-    d_pre_off_ = (uint32_t*)(a + off[PRE_OFF]); d_pre_nblk_ = (uint32_t*)(a + off[PRE_NBLK]);
-    d_pre_row_ = (uint32_t*)(a + off[PRE_ROW]); d_patch_ = (PatchRec*)(a + off[PATCH]);
-    d_tpl_ = a + off[TPL]; d_code_ = a + off[CODE]; d_tjob_ = (TplJob*)(a + off[TJOB]);
-    d_txraw_ = a + off[TXRAW]; d_wtx_ = (WtxRec*)(a + off[WTX]); d_wjob_ = (WinJob*)(a + off[WJOB]);
-    d_ljob_ = (LinJob*)(a + off[LJOB]);
-    d_hrow_ = (uint32_t*)(a + off[HROW]); d_hprog_ = a + off[HPROG];
-    d_zeros_ = a + off[ZEROS]; d_intab_ = (uint32_t*)(a + off[INTAB]); d_txd_ = a + off[TXD];
-    d_emap_ = need_e ? (uint32_t*)(a + off[EMAP]) : nullptr;
-    d_mmap_ = need_mm ? (uint32_t*)(a + off[MMAP]) : nullptr;
-    uint8_t* h = (uint8_t*)host_image_;
-    memset(h + off[ZEROS], 0, 64);
-    // Per array, direct upload from the parts' page-locked arrays only in rounds of at least 64k
-    // rows and when the array's pieces are large:
-    // each piece is its own copy, and a copy costs a few microseconds on the issuing thread, while
-    // the team fills the image at several GB/s per thread (a 13k-input C3 round and the 65,536-check
-    // Taproot rounds measured slower direct, 1M C2 inputs faster: profiles/r06/ab/dropin_direct_*,
-    // c3_direct_upload.txt).  Small arrays go through the image, uploaded as one span.
-    constexpr size_t DIRECT_MIN_PIECE = (size_t)256 << 10, DIRECT_MIN_ROWS = 65536;
-    bool dm[NB] = {};
-    if (direct_arg && direct_upload() && P && R >= DIRECT_MIN_ROWS) {
-        for (int b : {TAG, X, RR, S, AUX, PRE, TPL, CODE, TXRAW, HPROG})
-            dm[b] = sizes[b] / P >= DIRECT_MIN_PIECE;
-    }
-    // the rows the host pass pre-uploaded per shard (pre_upload): gathered in the run, not sent
-    bool gathered = direct_arg && pre_armed_ && pre_P_ == P && R < ((size_t)1 << 32);
-    for (size_t p = 0; gathered && p < P; p++) gathered = pre_rows_[p] == Rw[p]->size();
-    pre_armed_ = false;
-    gather_pending_ = gathered;
-    if (gathered) {
-        gather_row0_.assign(row0.begin(), row0.end());
-        for (int b : {TAG, X, RR, S}) dm[b] = true;  // neither filled into the image nor uploaded
-    }
-    // the rows of part p in [lo, hi): the bulk of a tuple batch, copied in blocks by the team
-    auto fill_rows = [&](size_t p, size_t lo, size_t hi) {
-        const TupleRows& rw = *Rw[p];
-        const size_t r0 = row0[p] + lo, nr = hi - lo;
-        auto cp = [&](int b, size_t at, const void* src, size_t len) {
-            if (len) memcpy(h + off[b] + at, src, len);
-        };
-        if (!dm[TAG]) cp(TAG, r0, rw.tag.data() + lo, nr);
-        if (!dm[X]) cp(X, 32 * r0, rw.x.data() + 32 * lo, 32 * nr);
-        if (!dm[RR]) cp(RR, 32 * r0, rw.r.data() + 32 * lo, 32 * nr);
-        if (!dm[S]) cp(S, 32 * r0, rw.s.data() + 32 * lo, 32 * nr);
-        if (need_y && nr) rw.copy_y(h + off[Y] + 32 * r0, lo, hi);  // past the stored prefix: zero
-        if (need_m && nr) rw.copy_msg(h + off[M] + 32 * r0, lo, hi);  // past the stored prefix: ONE
-        if (need_e && nr) rw.copy_emap((uint32_t*)(h + off[EMAP]) + r0, lo, hi);
-        if (need_mm && nr) rw.copy_mmap((uint32_t*)(h + off[MMAP]) + r0, lo, hi);
-    };
-    // part p's jobs and key-hash records (offsets fixed up for the concatenation)
-    auto fill = [&](size_t p) {
-        const SighashJobs& j = *J[p];
-        const TupleRows& rw = *Rw[p];
-        const size_t r0 = row0[p];
-        auto cp = [&](int b, size_t at, const void* src, size_t len) {
-            if (len) memcpy(h + off[b] + at, src, len);
-        };
-        if (!dm[AUX]) cp(AUX, auxb0[p], j.aux.data(), j.aux.size());
-        if (!dm[PRE]) cp(PRE, preb0[p], j.pre.data(), j.pre.size());
-        if (!dm[TPL]) cp(TPL, tpl0[p], j.tpl.data(), j.tpl.size());
-        if (!dm[CODE]) cp(CODE, code0[p], j.code.data(), j.code.size());
-        if (!dm[TXRAW]) cp(TXRAW, raw0[p], j.txraw.data(), j.txraw.size());
-        if (!dm[HPROG]) cp(HPROG, 20 * h0[p], rw.hprog.data(), rw.hprog.size());
-        const uint32_t ablk = (uint32_t)(auxb0[p] / 64), pblk = (uint32_t)(preb0[p] / 64);
-        uint32_t* ao = (uint32_t*)(h + off[AUX_OFF]) + auxi0[p];
-        for (size_t k = 0; k < j.aux_off.size(); k++) ao[k] = j.aux_off[k] + ablk;
-        cp(AUX_NBLK, 4 * auxi0[p], j.aux_nblk.data(), 4 * j.aux_nblk.size());
-        uint32_t* po = (uint32_t*)(h + off[PRE_OFF]) + prei0[p];
-        uint32_t* pr = (uint32_t*)(h + off[PRE_ROW]) + prei0[p];
-        for (size_t k = 0; k < j.pre_off.size(); k++) {
-            po[k] = j.pre_off[k] + pblk;
-            pr[k] = j.pre_row[k] + (uint32_t)r0;
-        }
-        cp(PRE_NBLK, 4 * prei0[p], j.pre_nblk.data(), 4 * j.pre_nblk.size());
-        PatchRec* pt = (PatchRec*)(h + off[PATCH]) + pat0[p];
-        for (size_t k = 0; k < j.patches.size(); k++)
-            pt[k] = PatchRec{j.patches[k].pre_byte + pblk * 64, j.patches[k].aux + (uint32_t)auxi0[p]};
-        TplJob* tj = (TplJob*)(h + off[TJOB]) + tj0[p];
-        size_t wb = 0, tb = 0;
-        for (size_t k = 0; k < j.tjobs.size(); k++) {
-            TplJob t = j.tjobs[k];
-            tb += tpl_job_blocks(t);
-            t.tpl_off += (uint32_t)tpl0[p];
-            t.code_off += (uint32_t)code0[p];
-            t.row += (uint32_t)r0;
-            if (!need_mm) t.nblk &= ~TPL_EARLY;  // no early digests for this round: hash it here
-            tj[k] = t;
-        }
-        WtxRec* wr = (WtxRec*)(h + off[WTX]) + wtx0[p];
-        for (size_t k = 0; k < j.wtx.size(); k++) {
-            WtxRec t = j.wtx[k];
-            wb += t.tx_len + ((t.n_in & WTX_TABLE_ONLY) ? 0 : 96);
-            t.tx_off += (uint32_t)raw0[p];
-            t.in_base += (uint32_t)win0[p];
-            wr[k] = t;
-        }
-        WinJob* wj = (WinJob*)(h + off[WJOB]) + wj0[p];
-        for (size_t k = 0; k < j.wjobs.size(); k++) {
-            WinJob t = j.wjobs[k];
-            wb += t.code_len + sizeof(WinJob) + 32;
-            t.tx += (uint32_t)wtx0[p];
-            t.code_off += (uint32_t)code0[p];
-            t.row += (uint32_t)r0;
-            wj[k] = t;
-        }
-        LinJob* lj = (LinJob*)(h + off[LJOB]) + lj0[p];
-        for (size_t k = 0; k < j.ljobs.size(); k++) {
-            LinJob t = j.ljobs[k];
-            wb += t.code_len + sizeof(LinJob) + 32;
-            t.tx += (uint32_t)wtx0[p];
-            t.code_off += (uint32_t)code0[p];
-            t.row += (uint32_t)r0;
-            lj[k] = t;
-        }
-        uint32_t* hr = (uint32_t*)(h + off[HROW]) + h0[p];
-        for (size_t k = 0; k < rw.hrow.size(); k++) hr[k] = rw.hrow[k] + (uint32_t)r0;
-        part_tjblk[p] = tb;
-        part_wbytes[p] = wb;
-    };
-    // work items: blocks of <= 64k rows of every part, then every part's jobs
-    struct Work {
-        size_t p, lo, hi;  // hi == 0: part p's jobs
-    };
-    std::vector<Work> work;
-    constexpr size_t RB = (size_t)1 << 16;
-    if (!dm[TAG] || !dm[X] || !dm[RR] || !dm[S] || need_y || need_m || need_e || need_mm)
-        for (size_t p = 0; p < P; p++)
-            for (size_t lo = 0, nr = Rw[p]->size(); lo < nr; lo += RB)
-                work.push_back(Work{p, lo, std::min(nr, lo + RB)});
-    for (size_t p = 0; p < P; p++) work.push_back(Work{p, 0, 0});
-    auto run_work = [&](const Work& w) {
-        if (w.hi) fill_rows(w.p, w.lo, w.hi);
-        else fill(w.p);
-    };
-    const size_t want = tl_stage_threads ? tl_stage_threads : std::max<size_t>(P, 16);
-    const size_t nth = std::min(work.size(), want);
-    if (nth <= 1 || upload < ((size_t)1 << 20)) {
-        for (const Work& w : work) run_work(w);
-    } else {
-        host::run_team((unsigned)nth, [&](unsigned t) {
-            for (size_t k = t; k < work.size(); k += nth) run_work(work[k]);
-        });
-    }
-    tjob_blocks_ = 0;
-    sighash_bytes_ = 0;
-    for (size_t p = 0; p < P; p++) {
-        tjob_blocks_ += part_tjblk[p];
-        sighash_bytes_ += part_wbytes[p];
-    }
-    sighash_bytes_ += 64 * (pre_blocks_ + aux_blocks_ + tjob_blocks_) + 32 * (n_pre_ + n_aux_ + n_tjob_);
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    // the copy is issued by the next run, in two parts on the two streams that need them first
-    // (upload_on): the tuple rows on the side stream ahead of K_inv / K_tkey / the Q ladder, the
-    // sighash inputs on the main stream ahead of the front kernel
-    up_pending_ = true;
-    up_copies_.clear();
-    // The tuple rows first, then the sighash inputs: the copies of all streams leave in issue order
-    // (one copy queue), and K_inv / K_keyq -- the round's long pole -- wait only for the rows
-    // (round 6: issued part by part, rows and sighash inputs interleaved, the rows of a 500k-input
-    // round landed 2.4 instead of ~1 ms after the upload began).  Each class: the image's spans (runs
-    // of arrays not uploaded directly), then each part's own piece of every direct array.
-    auto spans = [&](int lo, int hi) {
-        for (int b = lo; b < hi;) {
-            if (dm[b]) {
-                b++;
-                continue;
-            }
-            int e = b + 1;
-            while (e < hi && !dm[e]) e++;
-            if (off[e] > off[b]) up_copies_.push_back(UpCopy{off[b], h + off[b], off[e] - off[b], lo < AUX});
-            b = e;
-        }
-    };
-    auto piece = [&](int b, size_t at, const void* src, size_t len) {
-        if (dm[b] && len) up_copies_.push_back(UpCopy{off[b] + at, src, len, b < AUX});
-    };
-    spans(0, AUX);
-    for (size_t p = 0; p < P && !gathered; p++) {
-        const TupleRows& rw = *Rw[p];
-        const size_t nr = rw.size();
-        piece(TAG, row0[p], rw.tag.data(), nr);
-        piece(X, 32 * row0[p], rw.x.data(), 32 * nr);
-        piece(RR, 32 * row0[p], rw.r.data(), 32 * nr);
-        piece(S, 32 * row0[p], rw.s.data(), 32 * nr);
-    }
-    spans(AUX, UPLOADED);
-    for (size_t p = 0; p < P; p++) {
-        const TupleRows& rw = *Rw[p];
-        const SighashJobs& j = *J[p];
-        piece(AUX, auxb0[p], j.aux.data(), j.aux.size());
-        piece(PRE, preb0[p], j.pre.data(), j.pre.size());
-        piece(TPL, tpl0[p], j.tpl.data(), j.tpl.size());
-        piece(CODE, code0[p], j.code.data(), j.code.size());
-        piece(TXRAW, raw0[p], j.txraw.data(), j.txraw.size());
-        piece(HPROG, 20 * h0[p], rw.hprog.data(), rw.hprog.size());
-    }
-    if (need_y) BCC_HIP_TRY(hipMemcpy(a + off[Y], h + off[Y], 32 * R, hipMemcpyHostToDevice));
-    // every row's msg is uint256 ONE (byte 0 = 1) unless a part stores its own; the sighash kernels
-    // overwrite theirs.  Set with the upload, on the stream of the kernels that write the rows
-    // (upload_on), so that staging never waits for the GPU.
-    up_msg_one_ = !need_m && R;
-    if (need_m) BCC_HIP_TRY(hipMemcpy(a + off[M], h + off[M], 32 * R, hipMemcpyHostToDevice));
-    return ensure_vbuf();
-}
-
-// Raw tuples (bcc_pubkey_verify_batch from host buffers): the caller's pubkey / signature blobs,
-// both offset arrays and the messages are copied as they are into the pinned image (by the team, in
-// 2 MiB pieces), go up in one DMA copy, and K_der writes the rows on the device (run_ecdsa).  The
-// host neither parses nor touches a row.
-int DeviceBatch::stage_der(const DerTuples& t) {
-    if (int e = sync()) return e;
-    const size_t R = t.n;
-    const uint64_t pb = t.pub_bytes(), sb = t.sig_bytes();
-    n_rows_ = R;
-    n_pre_ = n_aux_ = n_patch_ = pre_blocks_ = aux_blocks_ = n_tjob_ = tjob_blocks_ = 0;
-    n_wtx_ = n_wjob_ = n_ljob_ = n_win_ = n_hash_ = sighash_bytes_ = 0;
-    d_emap_ = nullptr;
-    n_der_ = 0;
-    enum { PUB, SIG, POFF, SOFF, M, UPLOADED, TAG = UPLOADED, X, Y, RR, S, V, NB };
-    size_t sizes[NB] = {};
-    sizes[PUB] = pb; sizes[SIG] = sb; sizes[POFF] = sizes[SOFF] = 8 * (R + 1);
-    sizes[M] = sizes[X] = sizes[Y] = sizes[RR] = sizes[S] = 32 * R;
-    sizes[TAG] = sizes[V] = R;
-    size_t off[NB], total = 0;
-    for (int i = 0; i < NB; i++) {
-        off[i] = total;
-        total += align256(sizes[i]);
-    }
-    const size_t upload = off[UPLOADED];
-    if (total > cap_) {
-        if (arena_) BCC_HIP_TRY(hipFree(arena_));
-        arena_ = nullptr;
-        cap_ = 0;
-        BCC_HIP_TRY(hipMalloc(&arena_, total));
-        cap_ = total;
-    }
-    if (upload > host_cap_) {
-        if (host_image_) BCC_HIP_TRY(hipHostFree(host_image_));
-        host_image_ = nullptr;
-        host_cap_ = 0;
-        BCC_HIP_TRY(hipHostMalloc(&host_image_, upload, hipHostMallocDefault));
-        host_cap_ = upload;
-    }
-    uint8_t* a = (uint8_t*)arena_;
-    d_tag = a + off[TAG]; d_x = a + off[X]; d_y = a + off[Y]; d_r = a + off[RR]; d_s = a + off[S];
-    d_m = a + off[M]; d_v = a + off[V];
-    d_pub_ = a + off[PUB]; d_sig_ = a + off[SIG];
-    d_pub_off_ = (const uint64_t*)(a + off[POFF]); d_sig_off_ = (const uint64_t*)(a + off[SOFF]);
-    uint8_t* h = (uint8_t*)host_image_;
-    struct Piece {
-        uint8_t* dst;
-        const uint8_t* src;
-        size_t len;
-    };
-    std::vector<Piece> work;
-    constexpr size_t PIECE = (size_t)2 << 20;
-    auto add = [&](int b, const void* src, size_t len) {
-        for (size_t o = 0; o < len; o += PIECE)
-            work.push_back(Piece{h + off[b] + o, (const uint8_t*)src + o, std::min(PIECE, len - o)});
-    };
-    add(PUB, t.pub_blob + t.pub_off[0], pb);
-    add(SIG, t.sig_blob + t.sig_off[0], sb);
-    add(POFF, t.pub_off, 8 * (R + 1));
-    add(SOFF, t.sig_off, 8 * (R + 1));
-    add(M, t.msg32, 32 * R);
-    const size_t want = tl_stage_threads ? tl_stage_threads : 16;
-    const size_t nth = std::min(work.size(), want);
-    if (nth <= 1) {
-        for (const Piece& w : work) memcpy(w.dst, w.src, w.len);
-    } else {
-        host::run_team((unsigned)nth, [&](unsigned k0) {
-            for (size_t k = k0; k < work.size(); k += nth) memcpy(work[k].dst, work[k].src, work[k].len);
-        });
-    }
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    up_pending_ = true;
-    up_msg_one_ = false;
-    up_copies_.assign(1, UpCopy{0, host_image_, upload, true});
-    n_der_ = R;
-    pub_base_ = t.pub_off[0];
-    pub_bytes_ = pb;
-    sig_base_ = t.sig_off[0];
-    sig_bytes_ = sb;
-    return ensure_vbuf();
-}
-
-// The staged image's pending upload: all of it on `rows_stream` when `rest_stream` is null, else
-// the tuple rows on `rows_stream` and the rest on `rest_stream`.  Stream order puts every kernel
-// launched after it on the same stream behind its bytes.
-// Per-shard row pre-upload (DeviceBatch::pre_arm / pre_upload).  Shard buffer layout for cap rows:
-// tag at 0, then x, r, s (32 bytes a row each) from align256(cap).
-static size_t pre_x_off(size_t cap) { return (cap + 255) & ~(size_t)255; }
-int DeviceBatch::pre_arm(unsigned P, size_t cap_rows) {
-    pre_armed_ = false;
-    gather_pending_ = false;
-    if (P == 0 || P > PRE_MAX_SHARDS || cap_rows == 0) return 0;
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    if (!pre_stream_) {
-        hipStream_t st = nullptr;
-        hipEvent_t e = nullptr;
-        BCC_HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        BCC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        pre_stream_ = st;
-        ev_pre_ = e;
-    }
-    // the buffers' previous round (its gather) and pre-uploads are done before they are rewritten
-    if (int e = sync()) return e;
-    BCC_HIP_TRY(hipStreamSynchronize((hipStream_t)pre_stream_));
-    if (cap_rows > pre_cap_ || pre_buf_.size() < P) {
-        const size_t cap = std::max(cap_rows, pre_cap_);
-        for (uint8_t*& b : pre_buf_) {
-            if (b) BCC_HIP_TRY(hipFree(b));
-            b = nullptr;
-        }
-        pre_buf_.assign(std::max<size_t>(P, pre_buf_.size()), nullptr);
-        pre_cap_ = 0;
-        for (uint8_t*& b : pre_buf_) BCC_HIP_TRY(hipMalloc(&b, pre_x_off(cap) + 96 * cap));
-        pre_cap_ = cap;
-    }
-    pre_rows_.assign(P, SIZE_MAX);
-    pre_P_ = P;
-    pre_armed_ = true;
-    return 0;
-}
-
-void DeviceBatch::pre_upload(unsigned t, const TupleRows& rw) {
-    if (!pre_armed_ || t >= pre_P_) return;
-    const size_t n = rw.size();
-    if (n > pre_cap_) return;  // stays SIZE_MAX: this shard's rows go up with the round
-    if (hipSetDevice(dev_) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    hipStream_t st = (hipStream_t)pre_stream_;
-    uint8_t* b = pre_buf_[t];
-    const size_t xo = pre_x_off(pre_cap_);
-    bool ok = true;
-    if (n) {
-        ok = hipMemcpyAsync(b, rw.tag.data(), n, hipMemcpyHostToDevice, st) == hipSuccess &&
-             hipMemcpyAsync(b + xo, rw.x.data(), 32 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
-             hipMemcpyAsync(b + xo + 32 * pre_cap_, rw.r.data(), 32 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
-             hipMemcpyAsync(b + xo + 64 * pre_cap_, rw.s.data(), 32 * n, hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        return;
-    }
-    pre_rows_[t] = n;  // (each worker writes its own shard's entry; read after the pass joins)
-}
-
-// K_rowgather: the pre-uploaded shards' rows into the arena's tag / x / r / s, one lane per row.
-struct RowGather {
-    const uint8_t* base[64];
-    uint32_t row0[64 + 1];
-    uint32_t P;
-    uint32_t xoff;  // x's offset in a shard buffer; r, s follow at + 32 cap, + 64 cap
-    uint32_t cap;
-};
+// The small kernels of a round's plumbing (launched by device_batch.hip and taproot_round.hip).
+// K_rowgather (RowGather: sighash_kernels.h).
 __global__ void __launch_bounds__(256) row_gather_kernel(RowGather g, uint8_t* __restrict__ tag,
                                                         uint4* __restrict__ x, uint4* __restrict__ r,
                                                         uint4* __restrict__ s, uint32_t R) {
@@ -1761,128 +1003,6 @@ __global__ void __launch_bounds__(256) msg_one_kernel(uint4* __restrict__ m, siz
     if (k >= n) return;
     m[2 * k] = make_uint4(1u, 0u, 0u, 0u);
     m[2 * k + 1] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-int DeviceBatch::upload_on(hipStream_t rows_stream, hipStream_t rest_stream, int part) {
-    if (!up_pending_) return 0;
-    uint8_t* a = (uint8_t*)arena_;
-    // The rows first, and the rest only after them: copies queued on two streams share the copy
-    // engines, so K_inv / K_keyq would otherwise wait for most of the upload (a 500k-input round's
-    // rows landed after 2.3 of its 3.6 ms of copies).  run_stages issues the rows (part 1), queues
-    // the Q kernels behind them, then issues the rest (part 2): the ~50 copy calls of the rest no
-    // longer hold up the Q kernels' launch.
-    if (part & 1) {
-        if (gather_pending_) {  // the rows the host pass already sent, into place first
-            gather_pending_ = false;
-            BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_pre_, (hipStream_t)pre_stream_));
-            BCC_HIP_TRY(hipStreamWaitEvent(rows_stream, (hipEvent_t)ev_pre_, 0));
-            RowGather g{};
-            g.P = pre_P_;
-            g.xoff = (uint32_t)pre_x_off(pre_cap_);
-            g.cap = (uint32_t)pre_cap_;
-            for (unsigned p = 0; p < pre_P_; p++) {
-                g.base[p] = pre_buf_[p];
-                g.row0[p] = (uint32_t)gather_row0_[p];
-            }
-            g.row0[pre_P_] = (uint32_t)gather_row0_[pre_P_];
-            if (n_rows_) {
-                hipLaunchKernelGGL(row_gather_kernel, dim3((unsigned)((n_rows_ + 255) / 256)), dim3(256), 0,
-                                   rows_stream, g, (uint8_t*)d_tag, (uint4*)d_x, (uint4*)d_r, (uint4*)d_s,
-                                   (uint32_t)n_rows_);
-                BCC_HIP_TRY(hipGetLastError());
-            }
-        }
-        for (const UpCopy& c : up_copies_)
-            if (c.rows || !rest_stream)
-                BCC_HIP_TRY(hipMemcpyAsync(a + c.dst, c.src, c.len, hipMemcpyHostToDevice, rows_stream));
-        if (rest_stream) {
-            if (!ev_rows_up_) {
-                hipEvent_t e = nullptr;
-                BCC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                ev_rows_up_ = e;
-            }
-            BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_rows_up_, rows_stream));
-        }
-    }
-    if (part & 2) {
-        up_pending_ = false;
-        if (rest_stream) {
-            BCC_HIP_TRY(hipStreamWaitEvent(rest_stream, (hipEvent_t)ev_rows_up_, 0));
-            for (const UpCopy& c : up_copies_)
-                if (!c.rows)
-                    BCC_HIP_TRY(hipMemcpyAsync(a + c.dst, c.src, c.len, hipMemcpyHostToDevice, rest_stream));
-        }
-        if (up_msg_one_) {
-            up_msg_one_ = false;
-            hipStream_t ms = rest_stream ? rest_stream : rows_stream;
-            hipLaunchKernelGGL(msg_one_kernel, dim3((unsigned)((n_rows_ + 255) / 256)), dim3(256), 0, ms,
-                               (uint4*)d_m, n_rows_);
-            BCC_HIP_TRY(hipGetLastError());
-        }
-    }
-    return 0;
-}
-
-// K_win, K_lin, K2, K3: everything of the sighash stage after K_wtx / K1 / K3'.
-int DeviceBatch::launch_after_front(hipStream_t st) {
-    if (n_wjob_) {  // K_win: BIP143 preimages assembled from the raw tx bytes and hashed
-        hipLaunchKernelGGL(bip143_in_kernel, dim3((unsigned)((n_wjob_ + XS_WG - 1) / XS_WG)),
-                           dim3(XS_WG), 0, st, d_txraw_, d_wtx_, d_wjob_, (uint32_t)n_wjob_,
-                           d_intab_, d_txd_, d_code_, d_zeros_, d_m);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (n_ljob_) {  // K_lin: legacy NONE / SINGLE / ANYONECANPAY preimages from the raw tx bytes
-        hipLaunchKernelGGL(legacy_in_kernel, dim3((unsigned)((n_ljob_ + XS_WG - 1) / XS_WG)),
-                           dim3(XS_WG), 0, st, d_txraw_, d_wtx_, d_ljob_, (uint32_t)n_ljob_,
-                           d_intab_, d_code_, d_m);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (n_patch_) {
-        size_t th = n_patch_;
-        hipLaunchKernelGGL(patch_digests_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, st,
-                           d_pre_, d_patch_, d_auxd_, (uint32_t)n_patch_);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (n_pre_) {
-        hipLaunchKernelGGL(sha256d_msgs_kernel, dim3((unsigned)((n_pre_ + 255) / 256)), dim3(256), 0, st,
-                           d_pre_, d_pre_off_, d_pre_nblk_, (uint32_t)n_pre_, d_m, d_pre_row_);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-// The sighash stage with the front fused (sighash_front_kernel), then K_win, K2, K3.
-int DeviceBatch::launch_front(hipStream_t st) {
-    const size_t lanes = 3 * n_wtx_ + n_tjob_ + n_aux_;
-    if (lanes) {
-        hipLaunchKernelGGL(sighash_front_kernel, dim3((unsigned)((lanes + XS_WG - 1) / XS_WG)),
-                           dim3(XS_WG), 0, st, d_txraw_, d_wtx_, (uint32_t)n_wtx_, d_intab_, d_txd_,
-                           d_tpl_, d_code_, d_tjob_, (uint32_t)n_tjob_, d_aux_, d_aux_off_,
-                           d_aux_nblk_, (uint32_t)n_aux_, d_auxd_, d_m);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    return launch_after_front(st);
-}
-
-int DeviceBatch::run_sighash(void* stream) {
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    hipStream_t st = (hipStream_t)pick(stream);
-    if (!st) return (int)hipErrorOutOfMemory;
-    if (int e = upload_on(st, nullptr)) return e;
-    return launch_front(st);
-}
-
-int DeviceBatch::run_ecdsa(void* stream) {
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    void* st = pick(stream);
-    if (!st) return (int)hipErrorOutOfMemory;
-    if (int e = upload_on((hipStream_t)st, nullptr)) return e;
-    if (n_der_)  // raw tuples (stage_der): K_der writes the rows first
-        if (int e = der_launch(d_pub_, d_pub_off_, pub_base_, pub_bytes_, d_sig_, d_sig_off_, sig_base_,
-                               sig_bytes_, n_der_, d_tag, d_x, d_y, d_r, d_s, st))
-            return e;
-    if (int e = ecdsa_launch(scratch_, d_tag, d_x, d_y, d_r, d_s, d_m, d_v, n_rows_, st)) return e;
-    return launch_key_hash((hipStream_t)st);  // (run() queues the verdicts; the bench times this alone)
 }
 
 // K_h160: per key-hash condition (TupleRows::hrow) the HASH160 of the row's key, rebuilt from its
@@ -1920,14 +1040,6 @@ __global__ void __launch_bounds__(256) key_hash_kernel(const uint8_t* __restrict
     if (diff) verdict[row] = 0;
 }
 
-int DeviceBatch::launch_key_hash(hipStream_t st) {
-    if (!n_hash_) return 0;
-    hipLaunchKernelGGL(key_hash_kernel, dim3((unsigned)((n_hash_ + 255) / 256)), dim3(256), 0, st,
-                       d_tag, d_x, d_y, d_hrow_, d_hprog_, (uint32_t)n_hash_, d_v);
-    BCC_HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // n16 16-byte words from HBM into device-visible pinned host memory (verdicts: DeviceBatch and the
 // Taproot contexts).  A verdict region is 256-byte aligned and padded to the next region, so the
 // last word's tail bytes are in bounds on both sides (the host buffers are allocated in 16s).
@@ -1935,31 +1047,6 @@ __global__ void __launch_bounds__(256) bytes_to_host_kernel(const uint4* __restr
                                                             uint4* __restrict__ dst, uint32_t n16) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n16) dst[k] = src[k];
-}
-
-int DeviceBatch::ensure_vbuf() {
-    v_queued_ = false;
-    if (n_rows_ <= vcap_ && vbuf_dev_) return 0;
-    if (vbuf_) BCC_HIP_TRY(hipHostFree(vbuf_));
-    vbuf_ = nullptr;
-    vbuf_dev_ = nullptr;
-    vcap_ = 0;
-    const size_t cap = (std::max<size_t>(n_rows_, 1) + 15) & ~(size_t)15;
-    BCC_HIP_TRY(hipHostMalloc(&vbuf_, cap, hipHostMallocDefault));
-    BCC_HIP_TRY(hipHostGetDevicePointer(&vbuf_dev_, vbuf_, 0));
-    vcap_ = cap;
-    return 0;
-}
-
-int DeviceBatch::queue_verdicts(hipStream_t st) {
-    v_queued_ = false;
-    if (!n_rows_ || n_rows_ > vcap_ || !vbuf_dev_) return 0;  // fetch_verdicts copies instead
-    const uint32_t n16 = (uint32_t)((n_rows_ + 15) / 16);
-    hipLaunchKernelGGL(bytes_to_host_kernel, dim3((n16 + 255) / 256), dim3(256), 0, st,
-                       (const uint4*)d_v, (uint4*)vbuf_dev_, n16);
-    BCC_HIP_TRY(hipGetLastError());
-    v_queued_ = true;
-    return 0;
 }
 
 // Early sighashes (TPL_EARLY): row t's message from early row mmap[t] (DeviceBatch::early_launch).
@@ -1983,599 +1070,6 @@ __global__ void __launch_bounds__(256) late_msgs_kernel(const uint32_t* __restri
     uint4* dst = (uint4*)(m + 32 * (size_t)rows[k]);
     dst[0] = digs[2 * k];
     dst[1] = digs[2 * k + 1];
-}
-
-// Calls the late fill on the host (the GPU meanwhile runs what is queued), then one H2D copy of
-// the rows + digests and K_late on `st`.  The rows were range-checked against the staged batch.
-int DeviceBatch::put_late(hipStream_t st, const LateMsgFill* late) {
-    late_rows_.clear();
-    late_digs_.clear();
-    (*late)(late_rows_, late_digs_);
-    const size_t k = late_rows_.size();
-    if (k == 0) return 0;
-    if (late_digs_.size() != 32 * k) return (int)hipErrorInvalidValue;
-    for (uint32_t r : late_rows_)
-        if (r >= n_rows_) return (int)hipErrorInvalidValue;
-    const size_t dig_off = align256(4 * k);
-    if (k > late_cap_) {
-        if (late_host_) BCC_HIP_TRY(hipHostFree(late_host_));
-        if (late_dev_) BCC_HIP_TRY(hipFree(late_dev_));
-        late_host_ = nullptr;
-        late_dev_ = nullptr;
-        late_cap_ = 0;
-        BCC_HIP_TRY(hipHostMalloc(&late_host_, dig_off + 32 * k, hipHostMallocDefault));
-        BCC_HIP_TRY(hipMalloc(&late_dev_, dig_off + 32 * k));
-        late_cap_ = k;
-    }
-    uint8_t* h = (uint8_t*)late_host_;
-    memcpy(h, late_rows_.data(), 4 * k);
-    memcpy(h + dig_off, late_digs_.data(), 32 * k);
-    BCC_HIP_TRY(hipMemcpyAsync(late_dev_, h, dig_off + 32 * k, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(late_msgs_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st,
-                       (const uint32_t*)late_dev_, (const uint4*)(late_dev_ + dig_off), (uint32_t)k,
-                       d_m);
-    BCC_HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// K_inv and K_key read only the s and key rows, so they run on a side stream beside the sighash
-// kernels (fork / join by events: graph-capturable); prep + ladder wait for both.
-int DeviceBatch::run(void* stream, const LateMsgFill* late) {
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    hipStream_t st = (hipStream_t)pick(stream);
-    if (!st) return (int)hipErrorOutOfMemory;
-    if (n_rows_ == 0 || n_aux_ + n_tjob_ + n_pre_ + n_wjob_ + n_ljob_ == 0) {
-        if (int e = run_sighash(st)) return e;
-        if (late)
-            if (int e = put_late(st, late)) return e;
-        if (int e = run_ecdsa(st)) return e;  // K_h160 included
-        return queue_verdicts(st);
-    }
-    if (int e = run_stages(st, late)) return e;
-    if (!kh_done_)  // (else K_h160 ran ahead of the ladder, run_stages)
-        if (int e = launch_key_hash(st)) return e;
-    return queue_verdicts(st);
-}
-
-// Two streams: the sighash stage on the main stream (K_wtx + K3' + K1 fused into one front launch,
-// then K_win / K2 / K3), and on the side stream everything the message does not enter: K_inv,
-// then one launch with the key half of the prep, u2 and the Q ladder (ecdsa_launch_q); the G
-// ladder and K_tfin wait for both.  K_h160 needs only the key rows and the programs: it runs on the
-// main stream beside the Q ladder into verdicts preset to 1, and K_tfin then only clears failing
-// rows (verdict_and), instead of running after K_tfin at the end of the critical path.
-int DeviceBatch::run_stages(void* stream, const LateMsgFill* late) {
-    hipStream_t st = (hipStream_t)stream;
-    kh_done_ = false;
-    if (!side_stream_) {
-        hipStream_t s = nullptr;
-        hipEvent_t a = nullptr, b = nullptr, c = nullptr;
-        BCC_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        BCC_HIP_TRY(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-        BCC_HIP_TRY(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-        BCC_HIP_TRY(hipEventCreateWithFlags(&c, hipEventDisableTiming));
-        side_stream_ = s;
-        ev_fork_ = a;
-        ev_join_ = b;
-        ev_up_ = c;
-    }
-    hipStream_t side = (hipStream_t)side_stream_;
-    BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_fork_, st));
-    BCC_HIP_TRY(hipStreamWaitEvent(side, (hipEvent_t)ev_fork_, 0));
-    if (int e = upload_on(side, st, 1)) return e;
-    BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_up_, side));  // the tuple rows are on the device
-    if (int e = ecdsa_launch_pre(scratch_, d_s, n_rows_, side)) return e;
-    if (d_emap_ && early_n_) {  // rows with early twins: their K_keyq results are copied
-        BCC_HIP_TRY(hipStreamWaitEvent(side, (hipEvent_t)ev_early_, 0));
-        if (int e = ecdsa_launch_q_mapped(scratch_, early_scratch_, early_n_, d_emap_, d_tag, d_x, d_y,
-                                          d_r, d_s, n_rows_, side))
-            return e;
-    } else if (int e = ecdsa_launch_q(scratch_, d_tag, d_x, d_y, d_r, d_s, n_rows_, side)) {
-        return e;
-    }
-    BCC_HIP_TRY(hipEventRecord((hipEvent_t)ev_join_, side));
-    if (int e = upload_on(side, st, 2)) return e;  // the sighash inputs, behind the rows
-    if (int e = launch_front(st)) return e;
-    if (d_mmap_ && early_n_ && early_msgs_) {  // the early sighashes into their rows
-        BCC_HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)ev_early_sig_, 0));
-        BCC_HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)ev_up_, 0));  // the MMAP rows uploaded
-        hipLaunchKernelGGL(early_msgs_kernel, dim3((unsigned)((n_rows_ + 255) / 256)), dim3(256), 0, st,
-                           d_mmap_, (uint32_t)n_rows_, (uint32_t)early_n_, (const uint4*)early_msg_,
-                           (uint4*)d_m);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (n_hash_) {
-        BCC_HIP_TRY(hipMemsetAsync(d_v, 1, n_rows_, st));
-        BCC_HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)ev_up_, 0));  // K_h160 reads the key rows
-        if (int e = launch_key_hash(st)) return e;
-        kh_done_ = true;
-    }
-    if (late) {  // host-hashed messages: the host works while the queued kernels run
-        if (!n_hash_) BCC_HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)ev_up_, 0));  // rows uploaded
-        if (int e = put_late(st, late)) return e;
-    }
-    // (the wait for the Q launches, ev_join_, is placed by ecdsa_launch_after_pre: with a split
-    // K_keyq the G ladder of the whole rounds starts before the tail round's K_keyq is done)
-    return ecdsa_launch_after_pre(scratch_, d_tag, d_x, d_y, d_r, d_s, d_m, d_v, n_rows_, st,
-                                  kh_done_, ev_join_);
-}
-
-// Verdicts come back through a pinned buffer of the batch (an asynchronous copy on the run's stream,
-// then one host memcpy): a pageable D2H copy would pin the caller's pages on every call.
-int DeviceBatch::fetch_verdicts(uint8_t* out) {
-    if (!n_rows_) return sync();
-    if (v_queued_) {  // written into vbuf_ by the run's last kernel
-        v_queued_ = false;
-        BCC_HIP_TRY(hipSetDevice(dev_));
-        if (int e = wait(pick(last_stream_))) return e;
-        memcpy(out, vbuf_, n_rows_);
-        return 0;
-    }
-    BCC_HIP_TRY(hipSetDevice(dev_));
-    if (n_rows_ > vcap_)  // (stage sized it; kept in step with vbuf_dev_ either way)
-        if (int e = ensure_vbuf()) return e;
-    hipStream_t st = (hipStream_t)pick(last_stream_);
-    BCC_HIP_TRY(hipMemcpyAsync(vbuf_, d_v, n_rows_, hipMemcpyDeviceToHost, st));
-    if (int e = wait(st)) return e;
-    memcpy(out, vbuf_, n_rows_);
-    return 0;
-}
-
-int DeviceBatch::fetch_msgs(uint8_t* out) {
-    if (up_pending_) {  // staged but never run: the rows are still the host's
-        BCC_HIP_TRY(hipSetDevice(dev_));
-        hipStream_t st = (hipStream_t)pick(last_stream_);
-        if (int e = upload_on(st, nullptr)) return e;
-    }
-    if (int e = sync()) return e;
-    if (n_rows_) BCC_HIP_TRY(hipMemcpy(out, d_m, 32 * n_rows_, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int gpu_verify_batch(int device, const SighashJobs& jobs, const TupleRows& rows, uint8_t* verdict,
-                     double* stage_seconds) {
-    const SighashJobs* jp = &jobs;
-    const TupleRows* rp = &rows;
-    return gpu_verify_parts(device, &jp, &rp, 1, verdict, stage_seconds);
-}
-
-// one cached batch per (thread, device): repeated calls reuse the device arena, the pinned host
-// image, scratch and streams, and concurrent callers never share any of them
-thread_local std::vector<std::unique_ptr<DeviceBatch>> tl_batches;
-
-static DeviceBatch* thread_batch(int device) {
-    auto& cache = tl_batches;
-    if (device < 0) return nullptr;
-    if ((int)cache.size() <= device) cache.resize(device + 1);
-    if (!cache[device]) cache[device] = std::make_unique<DeviceBatch>(device);
-    return cache[device].get();
-}
-
-int gpu_early_launch(int device, const TupleRows* const* rows, size_t P, const SighashJobs* const* jobs) {
-    DeviceBatch* b = thread_batch(device);
-    if (!b) return (int)hipErrorInvalidDevice;
-    return b->early_launch(rows, P, jobs);
-}
-
-void gpu_early_reset(int device) {
-    if (device >= 0 && device < (int)tl_batches.size() && tl_batches[device]) tl_batches[device]->early_reset();
-}
-
-int gpu_verify_parts(int device, const SighashJobs* const* jobs, const TupleRows* const* rows,
-                     size_t parts, uint8_t* verdict, double* stage_seconds, const LateMsgFill* late) {
-    size_t n = 0;
-    for (size_t p = 0; p < parts; p++) n += rows[p]->size();
-    if (n == 0) return 0;
-    auto& cache = tl_batches;
-    if (device < 0) return (int)hipErrorInvalidDevice;
-    if ((int)cache.size() <= device) cache.resize(device + 1);
-    if (!cache[device]) cache[device] = std::make_unique<DeviceBatch>(device);
-    DeviceBatch& b = *cache[device];
-    auto t0 = std::chrono::steady_clock::now();
-    int e = b.stage_parts(jobs, rows, parts, true);  // the parts outlive this synchronous round
-    if (!e && stage_seconds)
-        *stage_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (!e) e = b.run(nullptr, late);
-    if (!e) e = b.fetch_verdicts(verdict);
-    if (e) cache[device].reset();  // a retry starts from a fresh batch (streams, arena, scratch)
-    return e;
-}
-
-int gpu_verify_der(int device, const DerTuples& t, uint8_t* verdict) {
-    if (t.n == 0) return 0;
-    DeviceBatch* b = thread_batch(device);
-    if (!b) return (int)hipErrorInvalidDevice;
-    BCC_HIP_TRY(hipSetDevice(device));
-    int e = b->stage_der(t);
-    if (!e) e = b->run(nullptr, nullptr);
-    if (!e) e = b->fetch_verdicts(verdict);
-    if (e) tl_batches[device].reset();  // a retry starts from a fresh batch
-    return e;
-}
-
-struct StagedRound {
-    int dev;
-    std::unique_ptr<DeviceBatch> b;
-};
-
-StagedRound* gpu_staged_new(int device) { return new StagedRound{device, nullptr}; }
-void gpu_staged_free(StagedRound* s) { delete s; }
-
-int gpu_staged_stage(StagedRound* s, const SighashJobs* const* jobs, const TupleRows* const* rows,
-                     size_t parts, double* stage_seconds) {
-    if (s->dev < 0) return (int)hipErrorInvalidDevice;
-    BCC_HIP_TRY(hipSetDevice(s->dev));
-    if (!s->b) s->b = std::make_unique<DeviceBatch>(s->dev);
-    auto t0 = std::chrono::steady_clock::now();
-    int e = s->b->stage_parts(jobs, rows, parts, true);  // held until gpu_staged_finish (pipeline.h)
-    if (!e && stage_seconds)
-        *stage_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (e) s->b.reset();
-    return e;
-}
-
-int gpu_staged_stage_der(StagedRound* s, const DerTuples& t, double* stage_seconds) {
-    if (s->dev < 0) return (int)hipErrorInvalidDevice;
-    BCC_HIP_TRY(hipSetDevice(s->dev));
-    if (!s->b) s->b = std::make_unique<DeviceBatch>(s->dev);
-    auto t0 = std::chrono::steady_clock::now();
-    int e = s->b->stage_der(t);
-    if (!e && stage_seconds)
-        *stage_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (e) s->b.reset();
-    return e;
-}
-
-int gpu_staged_pre_arm(StagedRound* s, unsigned P, size_t cap_rows) {
-    if (s->dev < 0) return (int)hipErrorInvalidDevice;
-    BCC_HIP_TRY(hipSetDevice(s->dev));
-    if (!s->b) s->b = std::make_unique<DeviceBatch>(s->dev);
-    const int e = s->b->pre_arm(P, cap_rows);
-    if (e) s->b.reset();
-    return e;
-}
-
-void gpu_staged_pre_upload(StagedRound* s, unsigned t, const TupleRows& rows) {
-    if (s->b) s->b->pre_upload(t, rows);
-}
-
-int gpu_staged_launch(StagedRound* s, const LateMsgFill* late) {
-    if (!s->b) return (int)hipErrorInvalidValue;
-    int e = s->b->run(nullptr, late);
-    if (e) s->b.reset();
-    return e;
-}
-
-int gpu_staged_finish(StagedRound* s, uint8_t* verdict) {
-    if (!s->b) return (int)hipErrorInvalidValue;
-    int e = s->b->fetch_verdicts(verdict);
-    if (e) s->b.reset();
-    return e;
-}
-
-int gpu_staged_run(StagedRound* s, uint8_t* verdict, const LateMsgFill* late) {
-    if (int e = gpu_staged_launch(s, late)) return e;
-    return gpu_staged_finish(s, verdict);
-}
-
-// ------------------------------------------------------------------------------------------
-// BIP341 / BIP342 batch (host/taproot.cpp builds the jobs).
-void tapsighash_midstate(uint32_t out[8]) {
-    uint8_t th[32];
-    host::sha256(reinterpret_cast<const uint8_t*>("TapSighash"), 10, th);
-    uint32_t w[16];
-    for (int k = 0; k < 16; k++) {
-        const uint8_t* b = th + 4 * (k & 7);
-        w[k] = (uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3];
-    }
-    sha256_init_state(out);
-    sha256_compress(out, w);
-}
-
-namespace {
-
-// Per (thread, device) state of gpu_taproot_verify: stream, kernel scratch, device arena and its
-// pinned host image, grown on demand and reused by later calls.
-struct TaprootCtx {
-    int dev = -1;
-    hipStream_t stream = nullptr;
-    size_t n = 0, off_verdict = 0, off_msg = 0;  // the round launched by gpu_taproot_begin
-    size_t xout = 0;  // its guest stage's bytes behind the verdicts in vpin (16-aligned start)
-    bool live = false;  // a round (rows or a guest stage) was queued and not yet ended
-    SigScratch sc;
-    void* arena = nullptr;
-    size_t cap = 0;
-    void* image = nullptr;
-    size_t image_cap = 0;
-    // pinned verdicts, written by a kernel queued right behind the round's kernels
-    // (gpu_taproot_begin): a copy-engine D2H would sit in the one copy queue and hold up the next
-    // round's upload until this round's kernels finish (measured: rounds serialised, 16.5 -> 20 ms
-    // per 1M checks), and issued later it waits behind that upload instead
-    uint8_t* vpin = nullptr;
-    uint8_t* vpin_dev = nullptr;  // the same pages as the device sees them
-    size_t vcap = 0;
-    ~TaprootCtx() {
-        if (dev >= 0) (void)hipSetDevice(dev);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (arena) (void)hipFree(arena);
-        if (image) (void)hipHostFree(image);
-        if (vpin) (void)hipHostFree(vpin);
-    }
-};
-
-}  // namespace
-
-int gpu_taproot_verify(int device, const TaprootJobs& J, uint8_t* verdict, uint8_t* msg32_out) {
-    const TaprootJobs* p = &J;
-    return gpu_taproot_verify_parts(device, &p, 1, verdict, msg32_out);
-}
-
-// The parts (one per host thread) are concatenated straight into the pinned image, each part by
-// its own thread with its index fix-ups (no merged host copy), then go to HBM in one DMA copy.
-// Per (thread, device) TAPROOT_SLOTS contexts: the pipelined rounds of bcc_taproot_verify_batch
-// rotate through them, so one round's upload runs beside the previous round's kernels while the
-// host builds the next one.
-thread_local std::unique_ptr<TaprootCtx> tl_taproot_ctxs[64][TAPROOT_SLOTS];
-
-// Frees the calling thread's device batches and Taproot contexts (bcc_release_thread_state).
-void release_device_thread_state() {
-    tl_batches.clear();
-    for (auto& d : tl_taproot_ctxs)
-        for (auto& c : d) c.reset();
-}
-
-int gpu_taproot_verify_parts(int device, const TaprootJobs* const* Jp, size_t P, uint8_t* verdict,
-                             uint8_t* msg32_out) {
-    if (int e = gpu_taproot_begin(device, 0, Jp, P)) return e;
-    return gpu_taproot_end(device, 0, verdict, msg32_out);
-}
-
-int gpu_taproot_begin(int device, int slot, const TaprootJobs* const* Jp, size_t P) {
-    return gpu_taproot_begin_extra(device, slot, Jp, P, nullptr);
-}
-
-int gpu_taproot_end(int device, int slot, uint8_t* verdict, uint8_t* msg32_out) {
-    return gpu_taproot_end_extra(device, slot, verdict, msg32_out, nullptr);
-}
-
-int gpu_taproot_begin_extra(int device, int slot, const TaprootJobs* const* Jp, size_t P,
-                            const TaprootExtra* X) {
-    std::vector<size_t> row0(P + 1, 0), aux0(P + 1, 0), msg0(P + 1, 0), auxi0(P + 1, 0),
-        msgi0(P + 1, 0), pat0(P + 1, 0), raw0(P + 1, 0), ttx0(P + 1, 0), tj0(P + 1, 0),
-        ext0(P + 1, 0), in0(P + 1, 0);
-    for (size_t q = 0; q < P; q++) {
-        const TaprootJobs& J = *Jp[q];
-        row0[q + 1] = row0[q] + J.rows();
-        aux0[q + 1] = aux0[q] + J.aux.size();
-        msg0[q + 1] = msg0[q] + J.msg.size();
-        auxi0[q + 1] = auxi0[q] + J.aux_off.size();
-        msgi0[q + 1] = msgi0[q] + J.msg_off.size();
-        pat0[q + 1] = pat0[q] + J.patches.size();
-        raw0[q + 1] = raw0[q] + J.dev.txraw.size();
-        ttx0[q + 1] = ttx0[q] + J.dev.ttx.size();
-        tj0[q + 1] = tj0[q] + J.dev.jobs.size();
-        ext0[q + 1] = ext0[q] + J.dev.ext.size();
-        in0[q + 1] = in0[q] + J.dev.in_entries;
-    }
-    const size_t n = row0[P];
-    if (device < 0 || device >= 64 || slot < 0 || slot >= TAPROOT_SLOTS) return (int)hipErrorInvalidDevice;
-    if (n == 0 && !X) {
-        if (tl_taproot_ctxs[device][slot]) {
-            tl_taproot_ctxs[device][slot]->n = 0;
-            tl_taproot_ctxs[device][slot]->live = false;
-        }
-        return 0;
-    }
-    if (aux0[P] >= ((size_t)1 << 32) || msg0[P] >= ((size_t)1 << 32) || raw0[P] >= ((size_t)1 << 32) ||
-        ext0[P] >= ((size_t)1 << 32)) {
-        fprintf(stderr, "[bcc] gpu_taproot_verify: a message blob exceeds 4 GiB; split the batch\n");
-        return (int)hipErrorInvalidValue;
-    }
-    auto& slot_ctx = tl_taproot_ctxs[device][slot];
-    if (!slot_ctx) {
-        auto c = std::make_unique<TaprootCtx>();
-        c->dev = device;
-        BCC_HIP_TRY(hipSetDevice(device));
-        BCC_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        slot_ctx = std::move(c);
-    }
-    TaprootCtx& c = *slot_ctx;
-    c.n = 0;
-    c.xout = 0;
-    c.live = false;
-    // this slot's previous round must be done with the arena and the pinned image
-    if (hipStreamSynchronize(c.stream) != hipSuccess) {
-        slot_ctx.reset();
-        return (int)hipErrorLaunchFailure;
-    }
-    BCC_HIP_TRY(hipSetDevice(device));
-    const size_t naux = auxi0[P], nmsg = msgi0[P], npat = pat0[P], nttx = ttx0[P], ntj = tj0[P];
-    // layout: sig64 | pk32 | msg32 | verdict | aux | msg | aux_off | aux_nblk | msg_off |
-    //         msg_nblk | msg_row | patches | txraw | TtxRec | TapJob | ext | guest upload ||
-    //         aux digests | input table | tx digests | guest device block (the last four not uploaded)
-    enum { SIG, PK, MSG, VER, AUX, MSGB, AUX_OFF, AUX_NBLK, MSG_OFF, MSG_NBLK, MSG_ROW, PATCH, TXRAW,
-           TTX, TJOB, EXT, XUP, UPLOADED, AUXD = UPLOADED, INTAB, TTXD, XDEV, NB };
-    size_t sizes[NB] = {};
-    sizes[SIG] = 64 * n; sizes[PK] = 32 * n; sizes[MSG] = 32 * n; sizes[VER] = n;
-    sizes[AUX] = aux0[P]; sizes[MSGB] = msg0[P]; sizes[AUX_OFF] = sizes[AUX_NBLK] = 4 * naux;
-    sizes[MSG_OFF] = sizes[MSG_NBLK] = sizes[MSG_ROW] = 4 * nmsg;
-    sizes[PATCH] = sizeof(PatchRec) * npat; sizes[TXRAW] = raw0[P] + 64;
-    sizes[TTX] = sizeof(TtxRec) * nttx; sizes[TJOB] = sizeof(TapJob) * ntj; sizes[EXT] = ext0[P];
-    sizes[AUXD] = 32 * naux; sizes[INTAB] = 16 * in0[P]; sizes[TTXD] = 160 * nttx;
-    const size_t xout = X ? (X->out_bytes + 15) & ~(size_t)15 : 0;
-    if (X) {
-        sizes[XUP] = X->up_bytes;
-        sizes[XDEV] = std::max(X->dev_bytes, xout);
-    }
-    size_t off[NB], total = 0;
-    for (int i = 0; i < NB; i++) {
-        off[i] = total;
-        total += align256(sizes[i]);
-    }
-    const size_t upload = off[UPLOADED];
-    if (total > c.cap) {
-        if (c.arena) BCC_HIP_TRY(hipFree(c.arena));
-        c.arena = nullptr;
-        c.cap = 0;
-        BCC_HIP_TRY(hipMalloc(&c.arena, total));
-        c.cap = total;
-    }
-    if (upload > c.image_cap) {
-        if (c.image) BCC_HIP_TRY(hipHostFree(c.image));
-        c.image = nullptr;
-        c.image_cap = 0;
-        BCC_HIP_TRY(hipHostMalloc(&c.image, upload, hipHostMallocDefault));
-        c.image_cap = upload;
-    }
-    uint8_t* h = (uint8_t*)c.image;
-    if (nmsg) memset(h + off[MSG], 0, 32 * n);  // rows the host-built path leaves unhashed
-    memset(h + off[TXRAW] + raw0[P], 0, 64);   // a dword past the last tx for the wire walks
-    auto fill = [&](size_t q) {
-        const TaprootJobs& J = *Jp[q];
-        const size_t r0 = row0[q], nr = J.rows();
-        auto cp = [&](int b, size_t at, const void* src, size_t len) {
-            if (len) memcpy(h + off[b] + at, src, len);
-        };
-        cp(SIG, 64 * r0, J.sig64.data(), 64 * nr);
-        cp(PK, 32 * r0, J.pk32.data(), 32 * nr);
-        cp(AUX, aux0[q], J.aux.data(), J.aux.size());
-        cp(MSGB, msg0[q], J.msg.data(), J.msg.size());
-        const uint32_t ablk = (uint32_t)(aux0[q] / 64), mblk = (uint32_t)(msg0[q] / 64);
-        uint32_t* ao = (uint32_t*)(h + off[AUX_OFF]) + auxi0[q];
-        for (size_t k = 0; k < J.aux_off.size(); k++) ao[k] = J.aux_off[k] + ablk;
-        cp(AUX_NBLK, 4 * auxi0[q], J.aux_nblk.data(), 4 * J.aux_nblk.size());
-        uint32_t* mo = (uint32_t*)(h + off[MSG_OFF]) + msgi0[q];
-        uint32_t* mr = (uint32_t*)(h + off[MSG_ROW]) + msgi0[q];
-        for (size_t k = 0; k < J.msg_off.size(); k++) {
-            mo[k] = J.msg_off[k] + mblk;
-            mr[k] = J.msg_row[k] + (uint32_t)r0;
-        }
-        cp(MSG_NBLK, 4 * msgi0[q], J.msg_nblk.data(), 4 * J.msg_nblk.size());
-        PatchRec* pt = (PatchRec*)(h + off[PATCH]) + pat0[q];
-        for (size_t k = 0; k < J.patches.size(); k++)
-            pt[k] = PatchRec{J.patches[k].pre_byte + mblk * 64, J.patches[k].aux + (uint32_t)auxi0[q]};
-        const TaprootTxJobs& D = J.dev;
-        cp(TXRAW, raw0[q], D.txraw.data(), D.txraw.size());
-        cp(EXT, ext0[q], D.ext.data(), D.ext.size());
-        TtxRec* tr = (TtxRec*)(h + off[TTX]) + ttx0[q];
-        for (size_t k = 0; k < D.ttx.size(); k++) {
-            TtxRec x = D.ttx[k];
-            x.tx_off += (uint32_t)raw0[q];
-            x.sp_off += (uint32_t)raw0[q];
-            x.in_base += (uint32_t)in0[q];
-            tr[k] = x;
-        }
-        TapJob* tj = (TapJob*)(h + off[TJOB]) + tj0[q];
-        for (size_t k = 0; k < D.jobs.size(); k++) {
-            TapJob x = D.jobs[k];
-            x.ttx += (uint32_t)ttx0[q];
-            x.row += (uint32_t)r0;
-            x.ext_off += (uint32_t)ext0[q];
-            tj[k] = x;
-        }
-    };
-    host::run_team((unsigned)P, [&](unsigned q) { fill(q); });
-    if (X && X->fill) X->fill(h + off[XUP]);
-    uint8_t* a = (uint8_t*)c.arena;
-    hipStream_t st = c.stream;
-    ShaMid mid;
-    tapsighash_midstate(mid.s);
-    BCC_HIP_TRY(hipMemcpyAsync(a, h, upload, hipMemcpyHostToDevice, st));
-    if (X && X->launch) {  // the guest stage: behind the upload, ahead of the ext blob's readers
-        if (int e = X->launch((void*)st, a + off[XUP], a + off[XDEV], a + off[EXT])) {
-            slot_ctx.reset();
-            return e;
-        }
-    }
-    if (nttx) {  // KT_tx, then KT_msg: the SigMsgs from the tx bytes
-        hipLaunchKernelGGL(taproot_tx_kernel, dim3((unsigned)((5 * nttx + XS_WG - 1) / XS_WG)),
-                           dim3(XS_WG), 0, st, a + off[TXRAW], (const TtxRec*)(a + off[TTX]),
-                           (uint32_t)nttx, (uint32_t*)(a + off[INTAB]), a + off[TTXD]);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (ntj) {
-        hipLaunchKernelGGL(taproot_msg_kernel, dim3((unsigned)((ntj + XS_WG - 1) / XS_WG)),
-                           dim3(XS_WG), 0, st, a + off[TXRAW], (const TtxRec*)(a + off[TTX]),
-                           (const TapJob*)(a + off[TJOB]), (uint32_t)ntj,
-                           (const uint32_t*)(a + off[INTAB]), a + off[TTXD], a + off[EXT],
-                           a + off[MSG], mid);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (naux) {
-        hipLaunchKernelGGL(sha256_aux_kernel, dim3((unsigned)((naux + 63) / 64)), dim3(64), 0, st,
-                           a + off[AUX], (const uint32_t*)(a + off[AUX_OFF]),
-                           (const uint32_t*)(a + off[AUX_NBLK]), (uint32_t)naux, a + off[AUXD]);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (npat) {
-        hipLaunchKernelGGL(patch_digests_kernel, dim3((unsigned)((npat + 255) / 256)), dim3(256), 0,
-                           st, a + off[MSGB], (const PatchRec*)(a + off[PATCH]), a + off[AUXD],
-                           (uint32_t)npat);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (nmsg) {
-        hipLaunchKernelGGL(tapsighash_kernel, dim3((unsigned)((nmsg + 255) / 256)), dim3(256), 0, st,
-                           a + off[MSGB], (const uint32_t*)(a + off[MSG_OFF]),
-                           (const uint32_t*)(a + off[MSG_NBLK]), (uint32_t)nmsg, a + off[MSG],
-                           (const uint32_t*)(a + off[MSG_ROW]), mid);
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (n) {
-        if (int e = schnorr_launch(c.sc, a + off[0], a + off[2], a + off[1], a + off[3], n, st)) {
-            slot_ctx.reset();
-            return e;
-        }
-    }
-    const size_t n16 = (n + 15) & ~(size_t)15;  // the guest's bytes follow the verdicts, 16-aligned
-    if (n16 + xout > c.vcap) {
-        if (c.vpin) BCC_HIP_TRY(hipHostFree(c.vpin));
-        c.vpin = nullptr;
-        c.vcap = 0;
-        BCC_HIP_TRY(hipHostMalloc((void**)&c.vpin, n16 + xout, hipHostMallocDefault));
-        BCC_HIP_TRY(hipHostGetDevicePointer((void**)&c.vpin_dev, c.vpin, 0));
-        c.vcap = n16 + xout;
-    }
-    if (n) {
-        hipLaunchKernelGGL(bytes_to_host_kernel, dim3((unsigned)((n16 / 16 + 255) / 256)), dim3(256), 0, st,
-                           (const uint4*)(a + off[3]), (uint4*)c.vpin_dev, (uint32_t)(n16 / 16));
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    if (xout) {
-        hipLaunchKernelGGL(bytes_to_host_kernel, dim3((unsigned)((xout / 16 + 255) / 256)), dim3(256), 0, st,
-                           (const uint4*)(a + off[XDEV]), (uint4*)(c.vpin_dev + n16), (uint32_t)(xout / 16));
-        BCC_HIP_TRY(hipGetLastError());
-    }
-    c.xout = X ? X->out_bytes : 0;
-    c.live = true;
-    c.n = n;
-    c.off_verdict = off[3];
-    c.off_msg = off[2];
-    return 0;
-}
-
-int gpu_taproot_end_extra(int device, int slot, uint8_t* verdict, uint8_t* msg32_out,
-                          uint8_t* extra_out) {
-    if (device < 0 || device >= 64 || slot < 0 || slot >= TAPROOT_SLOTS) return (int)hipErrorInvalidDevice;
-    auto& slot_ctx = tl_taproot_ctxs[device][slot];
-    if (!slot_ctx || !slot_ctx->live) return 0;
-    TaprootCtx& c = *slot_ctx;
-    BCC_HIP_TRY(hipSetDevice(device));
-    const uint8_t* a = (const uint8_t*)c.arena;
-    const size_t n = c.n, xout = c.xout;
-    c.n = 0;
-    c.xout = 0;
-    c.live = false;
-    int rc = 0;
-    // the verdicts' copy was queued by gpu_taproot_begin
-    if ((msg32_out && n && (rc = (int)hipMemcpyAsync(msg32_out, a + c.off_msg, 32 * n,
-                                                hipMemcpyDeviceToHost, c.stream))) ||
-        (rc = (int)hipStreamSynchronize(c.stream))) {
-        fprintf(stderr, "[bcc] gpu_taproot_verify failed: %d\n", rc);
-        slot_ctx.reset();  // a retry starts from a fresh stream / arena / scratch
-        return rc;
-    }
-    if (n) memcpy(verdict, c.vpin, n);
-    if (extra_out && xout) memcpy(extra_out, c.vpin + ((n + 15) & ~(size_t)15), xout);
-    return 0;
 }
 
 }  // namespace bcc

@@ -167,8 +167,6 @@ __global__ __launch_bounds__(256) void tweak_fin_kernel(u32* __restrict__ scratc
     }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Per-kernel event times of the calling thread's last entry-point call (bcc_commit_last_kernel_ms;
 // only with BCC_COMMIT_TIMING=1 in the environment: the events cost a few microseconds a launch).
 enum { KT_HASH = 0, KT_ADD = 1, KT_FIN = 2, KT_KERNELS = 3 };
@@ -261,10 +259,14 @@ void tuples_host(const uint8_t* q32, const uint8_t* par, const uint8_t* p32, con
 int tuples_rounds(int device, const uint8_t* q32, const uint8_t* par, const uint8_t* p32,
                   const uint8_t* t32, uint8_t* verdict, size_t n, size_t first, size_t count) {
     const size_t R = std::min(n, CURVE_CHUNK);
-    const size_t row = align256(32 * R), o_q = row, o_t = 2 * row, o_par = 3 * row,
-                 o_v = o_par + align256(R), o_s = o_v + align256(R);
+    // p | q | t | parity (uploaded) | verdict (downloaded) | curve scratch (device only)
+    enum { PK, Q, T, PAR, V, S, NB };
+    size_t sizes[NB] = {}, off[NB + 1];
+    sizes[PK] = sizes[Q] = sizes[T] = 32 * R; sizes[PAR] = sizes[V] = R; sizes[S] = scratch_bytes(R);
+    const size_t total = arena_layout(sizes, off, NB);
+    const size_t o_q = off[Q], o_t = off[T], o_par = off[PAR], o_v = off[V], o_s = off[S];
     void *dv = nullptr, *hv = nullptr, *sv = nullptr;
-    if (int e = tuple_thread_buffers(device, o_s + scratch_bytes(R), o_s, &dv, &hv, &sv)) return e;
+    if (int e = tuple_thread_buffers(device, total, o_s, &dv, &hv, &sv)) return e;
     uint8_t* d = (uint8_t*)dv;
     uint8_t* h = (uint8_t*)hv;
     hipStream_t st = (hipStream_t)sv;
@@ -344,14 +346,18 @@ int commit_round(int device, const bcc_taproot_commit* items, size_t n, int* ret
     size_t lb = 0, nd = 0;
     commit_plan(items, n, lanes.data(), &lb, &nd);
     // uploaded: lanes | p | q | parity | nodes | leaf;  device only: t, then downloaded: verdict | leaf hashes
-    const size_t row = align256(32 * n);
-    const size_t o_p = align256(sizeof(CommitLane) * n), o_q = o_p + row, o_par = o_q + row,
-                 o_nodes = o_par + align256(n), o_leaf = o_nodes + align256(32 * nd),
-                 o_up = o_leaf + align256(64 * lb), o_v = o_up, o_lh = o_v + align256(n),
-                 o_host = o_lh + row, o_t = o_host, o_s = o_t + row;
     const size_t stride = std::min(n, CURVE_CHUNK);
+    enum { LANES, PK, Q, PAR, NODES, LEAF, UPLOADED, V = UPLOADED, LH, HOSTED, T = HOSTED, S, NB };
+    size_t sizes[NB] = {}, off[NB + 1];
+    sizes[LANES] = sizeof(CommitLane) * n; sizes[PK] = sizes[Q] = sizes[LH] = sizes[T] = 32 * n;
+    sizes[PAR] = sizes[V] = n; sizes[NODES] = 32 * nd; sizes[LEAF] = 64 * lb;
+    sizes[S] = scratch_bytes(stride);
+    const size_t total = arena_layout(sizes, off, NB);
+    const size_t o_p = off[PK], o_q = off[Q], o_par = off[PAR], o_nodes = off[NODES], o_leaf = off[LEAF],
+                 o_up = off[UPLOADED], o_v = off[V], o_lh = off[LH], o_host = off[HOSTED], o_t = off[T],
+                 o_s = off[S];
     void *dv = nullptr, *hv = nullptr, *sv = nullptr;
-    if (int e = tuple_thread_buffers(device, o_s + scratch_bytes(stride), o_host, &dv, &hv, &sv))
+    if (int e = tuple_thread_buffers(device, total, o_host, &dv, &hv, &sv))
         return e;
     uint8_t* d = (uint8_t*)dv;
     uint8_t* h = (uint8_t*)hv;
@@ -478,15 +484,22 @@ int spend_begin(int device, int slot, const SpendRound& R) {
     if (lb >= ((size_t)1 << 32) || nd >= ((size_t)1 << 32)) return (int)hipErrorInvalidValue;
     // uploaded: lanes | p | q | parity | nodes | leaf | copies; device only: verdict | leaf hashes |
     // t | curve scratch
-    const size_t row = align256(32 * n);
-    const size_t o_p = align256(sizeof(CommitLane) * n), o_q = o_p + row, o_par = o_q + row,
-                 o_nodes = o_par + align256(n), o_leaf = o_nodes + align256(32 * nd),
-                 o_cp = o_leaf + align256(64 * lb), up = o_cp + align256(sizeof(LeafCopy) * nk);
     const size_t stride = std::min(n, CURVE_CHUNK);
-    const size_t d_v = 0, d_lh = align256(n), d_t = d_lh + row, d_s = d_t + row;
+    enum { LANES, PK, Q, PAR, NODES, LEAF, CP, NUP };
+    size_t usz[NUP] = {}, uoff[NUP + 1];
+    usz[LANES] = sizeof(CommitLane) * n; usz[PK] = usz[Q] = 32 * n; usz[PAR] = n;
+    usz[NODES] = 32 * nd; usz[LEAF] = 64 * lb; usz[CP] = sizeof(LeafCopy) * nk;
+    const size_t up = arena_layout(usz, uoff, NUP);
+    const size_t o_p = uoff[PK], o_q = uoff[Q], o_par = uoff[PAR], o_nodes = uoff[NODES],
+                 o_leaf = uoff[LEAF], o_cp = uoff[CP];
+    enum { V, LH, T, S, NDEV };
+    size_t dsz[NDEV] = {}, doff[NDEV + 1];
+    dsz[V] = n; dsz[LH] = dsz[T] = 32 * n; dsz[S] = scratch_bytes(stride);
+    const size_t dev_bytes = arena_layout(dsz, doff, NDEV);
+    const size_t d_v = doff[V], d_lh = doff[LH], d_t = doff[T], d_s = doff[S];
     TaprootExtra X;
     X.up_bytes = up;
-    X.dev_bytes = d_s + scratch_bytes(stride);
+    X.dev_bytes = dev_bytes;
     X.out_bytes = n;
     X.fill = [&](uint8_t* h) {
         memcpy(h, lanes.data(), sizeof(CommitLane) * n);

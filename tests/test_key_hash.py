@@ -1,6 +1,6 @@
 """The HASH160(pubkey) == program check of key-hash spends taken over by the device
 (bcc_set_device_key_hash; csrc/host/engine.cpp DeferringChecker::defer_key_hash, sighash.hip
-key_hash_kernel): spends whose signature is VALID for the key they carry but whose key hashes to
+key_hash_kernel, staged and launched by device_batch.hip): spends whose signature is VALID for the key they carry but whose key hashes to
 another program — only the key-hash check can reject them (the reference stops at OP_EQUALVERIFY,
 interpreter.cpp:871-884 for P2PKH, :1936-1945 for P2WPKH) — beside the same spends with the right
 program, for P2WPKH, P2SH-P2WPKH and P2PKH with compressed, uncompressed and hybrid keys.

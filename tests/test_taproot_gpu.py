@@ -1,5 +1,6 @@
 """GPU: BIP341/342 signature checks through the product C ABI (bcc_taproot_verify_batch:
-csrc/host/taproot.cpp + sighash.hip tapsighash / aux kernels + the BIP340 kernels) against the
+csrc/host/taproot.cpp + the device round of taproot_round.hip over sighash.hip's tapsighash / aux
+kernels + the BIP340 kernels) against the
 reference's CheckSchnorrSignature (interpreter.cpp:1678-1704): every committed case with its
 sighash, and a fresh random batch (valid + mutated) checked item by item against oracle/_ref."""
 import os
