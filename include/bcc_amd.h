@@ -271,6 +271,100 @@ typedef struct bcc_inputs_stats {
 /* Statistics of the calling thread's last bcc_verify_inputs_batch / bcc_verify_input call. */
 void bcc_last_inputs_stats(bcc_inputs_stats* out);
 
+/* ---- a block's transaction hashes and merkle commitments ---------------------------------------
+ * What a validator hashes around bcc_verify_inputs_batch: every transaction's txid (it names the
+ * spent outputs) and wtxid (primitives/transaction.cpp:67-83), the header's merkle root with the
+ * CVE-2012-2459 mutation test (consensus/merkle.cpp:45-84, validation.cpp:3364-3380) and the
+ * segwit coinbase commitment (validation.cpp:3575-3610, consensus/validation.h:161-179).
+ * All 32-byte hashes are raw digest bytes (uint256::begin() order): the order of a prevout's txid
+ * field and of the header's merkle field, not the reversed hex display.
+ *
+ * Conventions of the three entries: synchronous on `device`; -1 spreads whole blocks or contiguous
+ * item ranges over the bcc_set_devices() GPUs (bcc_merkle_root: one tree, the first of them).  They
+ * return 0, or -1 for null arrays or null item buffers (nothing is computed then), or -1 on a
+ * device failure under BCC_DEVICE_FAILURE_ERROR (then no output is meaningful).  A device round is
+ * the transactions of some whole blocks (bcc_tx_hashes_batch: of an item range), uploaded once with
+ * their witnesses, one SHA-256 lane per digest, then one launch per merkle level over every tree
+ * of the round.  Transactions whose digests need more than bcc_set_host_txhash_blocks() 64-byte
+ * blocks are hashed on the host while the kernel runs: a lane is one serial chain.  A round of at
+ * most the entries' small-round threshold of transactions (leaves), and a round the device could
+ * not deliver after one retry, is evaluated by the host over the same records; the threshold is the
+ * engine's own (2,048, provisional) unless bcc_set_host_small_round() is larger, and
+ * bcc_set_host_small_round(0) turns it off like every other.  The failure rules
+ * are the Taproot side's (above), bcc_debug_fail_device_rounds[_code] reaches these rounds too.
+ * Results never depend on the device set, the round cut, the thread count or any threshold. */
+typedef struct bcc_tx_ref { const unsigned char* tx; unsigned int tx_len; } bcc_tx_ref;
+/* txid_out / wtxid_out: 32 bytes per item, either may be NULL.  err_out[i]: 0, or
+ * bitcoinconsensus_ERR_TX_DESERIALIZE / ERR_TX_SIZE_MISMATCH by the rules of
+ * bitcoinconsensus.cpp:79-102 (hashes zero then).  txid = SHA-256d of the serialization without
+ * marker, flag and witnesses; wtxid = SHA-256d of all tx_len bytes (equal to txid for a tx
+ * without witness data). */
+int bcc_tx_hashes_batch(const bcc_tx_ref* items, size_t n, unsigned char* txid_out,
+                        unsigned char* wtxid_out, int* err_out, int device);
+
+/* ComputeMerkleRoot (consensus/merkle.cpp:45-62): n == 0 gives the zero hash; *mutated (may be
+ * NULL) as the reference sets it. */
+int bcc_merkle_root(const unsigned char* leaves32, size_t n, unsigned char* root32,
+                    int* mutated, int device);
+
+typedef struct bcc_block_ref {
+    const unsigned char* block; size_t block_len;   /* 80-byte header, CompactSize count, txs;
+                                                       a buffer of 2^31 bytes or more does not
+                                                       deserialize */
+    int segwit_active;                              /* nHeight >= SegwitHeight */
+    unsigned char* txid_out; size_t txid_cap;       /* optional: n_tx * 32 bytes are written when
+                                                       txid_cap >= n_tx, else none */
+} bcc_block_ref;
+typedef struct bcc_block_result {
+    int status;              /* BCC_BLOCK_* below: the first rule that applies */
+    unsigned int n_tx;
+    int commit_pos;          /* GetWitnessCommitmentIndex, -1: none */
+    unsigned char merkle_root[32], witness_root[32];  /* witness_root zero unless computed */
+} bcc_block_result;
+#define BCC_BLOCK_OK 0
+#define BCC_BLOCK_ERR_DESERIALIZE 1        /* short header, bad count, a tx that does not parse,
+                                              bytes left over */
+#define BCC_BLOCK_ERR_EMPTY 2              /* no transactions */
+#define BCC_BLOCK_ERR_MERKLE_ROOT 3        /* "bad-txnmrklroot" */
+#define BCC_BLOCK_ERR_DUPLICATE 4          /* "bad-txns-duplicate" (mutated) */
+#define BCC_BLOCK_ERR_WITNESS_NONCE_SIZE 5 /* "bad-witness-nonce-size" */
+#define BCC_BLOCK_ERR_WITNESS_MERKLE 6     /* "bad-witness-merkle-match" */
+#define BCC_BLOCK_ERR_UNEXPECTED_WITNESS 7 /* "unexpected-witness" */
+/* Per block, in the order Core applies the rules: the header root against header[36..68); the
+ * mutation flag; then, with segwit_active and a commitment output, the reserved value's shape
+ * (coinbase input 0's witness is exactly one 32-byte element) and SHA-256d(witness root ||
+ * reserved value) against scriptPubKey[6..38) of the last commitment output (the witness tree's
+ * own mutation flag is ignored); otherwise any transaction with witness data gives
+ * UNEXPECTED_WITNESS.  The engine's own rule: a coinbase with no inputs on a path that would read
+ * vin[0] gives WITNESS_NONCE_SIZE (Core rejects such a block earlier, "bad-txns-vin-empty").
+ * The witness tree is computed only for a block that reaches the commitment comparison.  A block
+ * that does not deserialize or is empty has n_tx 0, commit_pos -1 and zero roots. */
+int bcc_block_commitments_batch(const bcc_block_ref* blocks, size_t n, bcc_block_result* out,
+                                int device);
+typedef struct bcc_block_stats {
+    size_t blocks, txs;          /* blocks (trees for bcc_merkle_root) and transactions (leaves) */
+    size_t bytes_hashed;         /* message bytes of every SHA-256d: digests, 64 per tree node */
+    size_t device_rounds, host_rounds;  /* host_rounds: small rounds + failure fallbacks */
+    size_t host_long_txs;        /* transactions of device rounds hashed on the host */
+    size_t merkle_launches;      /* merkle level launches of the device rounds */
+    size_t device_retries;
+} bcc_block_stats;
+/* Statistics of the calling thread's last call of one of the three entries. */
+void bcc_last_block_stats(bcc_block_stats* out);
+/* Transactions per device round (0, the default: the engine's choice, 262,144; a block is never
+ * split).  For tests: a small value puts round cuts inside a small batch.  Returns 0. */
+int bcc_set_block_round(size_t txs);
+/* The long-chain threshold in 64-byte SHA-256 blocks (0: no transaction goes to the host).
+ * Returns 0. */
+int bcc_set_host_txhash_blocks(unsigned blocks);
+/* Where the calling thread's last call on one device spent its time, in milliseconds, summed over
+ * its device rounds.  Event times: ms6[0] the transaction hashing kernel, ms6[1] the merkle level
+ * launches, ms6[2] the uploads, ms6[3] the downloads; zeros unless BCC_BLOCK_TIMING=1 was in the
+ * environment when the library was loaded (the events cost a few microseconds each).  Host clocks:
+ * ms6[4] parsing the blocks or transactions, ms6[5] staging a round (records, tables, the
+ * page-locked image of the upload).  For tools/block_bench.py. */
+void bcc_block_last_timing_ms(double* ms6);
+
 /* Where the Taproot side's work ran. */
 typedef struct bcc_taproot_stats {
     size_t items, checks, commits;   /* signature rows and commitment lanes of the call */

@@ -1000,6 +1000,160 @@ def last_inputs_stats(library=None):
     return {k: getattr(s, k) for k, _ in InputsStats._fields_}
 
 
+# ---- a block's transaction hashes and merkle commitments (include/bcc_amd.h) -------------------
+BLOCK_OK = 0
+BLOCK_ERR_DESERIALIZE = 1
+BLOCK_ERR_EMPTY = 2
+BLOCK_ERR_MERKLE_ROOT = 3
+BLOCK_ERR_DUPLICATE = 4
+BLOCK_ERR_WITNESS_NONCE_SIZE = 5
+BLOCK_ERR_WITNESS_MERKLE = 6
+BLOCK_ERR_UNEXPECTED_WITNESS = 7
+HOST_TXHASH_BLOCKS_DEFAULT = 16  # csrc/host/block.cpp BCC_HOST_TXHASH_BLOCKS
+
+
+class TxRef(ctypes.Structure):
+    """include/bcc_amd.h bcc_tx_ref."""
+    _fields_ = [("tx", ctypes.c_char_p), ("tx_len", ctypes.c_uint)]
+
+
+class BlockRef(ctypes.Structure):
+    """include/bcc_amd.h bcc_block_ref."""
+    _fields_ = [("block", ctypes.c_char_p), ("block_len", ctypes.c_size_t),
+                ("segwit_active", ctypes.c_int), ("txid_out", ctypes.c_void_p),
+                ("txid_cap", ctypes.c_size_t)]
+
+
+class BlockResult(ctypes.Structure):
+    """include/bcc_amd.h bcc_block_result."""
+    _fields_ = [("status", ctypes.c_int), ("n_tx", ctypes.c_uint), ("commit_pos", ctypes.c_int),
+                ("merkle_root", ctypes.c_ubyte * 32), ("witness_root", ctypes.c_ubyte * 32)]
+
+
+class BlockStats(ctypes.Structure):
+    """include/bcc_amd.h bcc_block_stats."""
+    _fields_ = [(k, ctypes.c_size_t) for k in ("blocks", "txs", "bytes_hashed", "device_rounds",
+                                               "host_rounds", "host_long_txs", "merkle_launches",
+                                               "device_retries")]
+
+
+def _bind_block(L):
+    if getattr(L, "_bcc_block_bound", False):
+        return L
+    L.bcc_tx_hashes_batch.argtypes = [ctypes.POINTER(TxRef), ctypes.c_size_t, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    L.bcc_merkle_root.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p,
+                                  ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    L.bcc_block_commitments_batch.argtypes = [ctypes.POINTER(BlockRef), ctypes.c_size_t,
+                                              ctypes.POINTER(BlockResult), ctypes.c_int]
+    L.bcc_last_block_stats.argtypes = [ctypes.POINTER(BlockStats)]
+    L.bcc_last_block_stats.restype = None
+    L.bcc_set_block_round.argtypes = [ctypes.c_size_t]
+    L.bcc_set_host_txhash_blocks.argtypes = [ctypes.c_uint]
+    L.bcc_block_last_timing_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.bcc_block_last_timing_ms.restype = None
+    L._bcc_block_bound = True
+    return L
+
+
+def tx_hashes(txs, device=0, wtxid=True, library=None):
+    """bcc_tx_hashes_batch: the txid and (wtxid=True) the wtxid of each serialized transaction, as
+    raw digest bytes (the order of a prevout's txid field).  Returns (txids, wtxids, errs): lists of
+    32-byte strings (wtxids None with wtxid=False) and of the crate's error codes (0, or
+    Error.ERR_TX_DESERIALIZE / ERR_TX_SIZE_MISMATCH, whose hashes are zero)."""
+    n = len(txs)
+    keep = [bytes(t) for t in txs]
+    arr = (TxRef * max(n, 1))()
+    for i, t in enumerate(keep):
+        arr[i] = TxRef(t, len(t))
+    tb = ctypes.create_string_buffer(32 * max(n, 1))
+    wb = ctypes.create_string_buffer(32 * max(n, 1)) if wtxid else None
+    err = (ctypes.c_int * max(n, 1))()
+    L = _bind_block(library if library is not None else lib())
+    rc = L.bcc_tx_hashes_batch(arr, n, tb, wb, err, device)
+    if rc != 0:
+        raise RuntimeError(f"bcc_tx_hashes_batch failed: {rc}")
+    cut = lambda b: [b.raw[32 * i: 32 * i + 32] for i in range(n)]
+    return cut(tb), cut(wb) if wtxid else None, [err[i] for i in range(n)]
+
+
+def merkle_root(leaves, device=0, library=None):
+    """bcc_merkle_root: ComputeMerkleRoot over the 32-byte leaves (a list, or their concatenation).
+    Returns (root, mutated); no leaves give the zero hash."""
+    blob = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(leaves)
+    assert len(blob) % 32 == 0
+    root = ctypes.create_string_buffer(32)
+    mutated = ctypes.c_int(0)
+    L = _bind_block(library if library is not None else lib())
+    rc = L.bcc_merkle_root(blob, len(blob) // 32, root, ctypes.byref(mutated), device)
+    if rc != 0:
+        raise RuntimeError(f"bcc_merkle_root failed: {rc}")
+    return root.raw, bool(mutated.value)
+
+
+def block_commitments(blocks, device=0, txids=True, txid_cap=None, library=None):
+    """bcc_block_commitments_batch.  blocks: [(raw block bytes, segwit_active)].  Returns one dict
+    per block: status (BLOCK_*), n_tx, commit_pos, merkle_root, witness_root and, with txids=True,
+    txids (the block's txids as raw digest bytes; None when the block gave none).  txid_cap: the
+    capacity in transactions of every block's txid buffer (default: enough for any block)."""
+    n = len(blocks)
+    keep = [bytes(b) for b, _ in blocks]
+    arr = (BlockRef * max(n, 1))()
+    bufs = []
+    for i, raw in enumerate(keep):
+        cap = (len(raw) // 60 + 1 if txid_cap is None else txid_cap) if txids else 0
+        buf = ctypes.create_string_buffer(b"\xee" * (32 * max(cap, 1)), 32 * max(cap, 1)) if txids else None
+        bufs.append((buf, cap))
+        arr[i] = BlockRef(raw, len(raw), 1 if blocks[i][1] else 0,
+                          ctypes.cast(buf, ctypes.c_void_p) if txids else None, cap)
+    res = (BlockResult * max(n, 1))()
+    L = _bind_block(library if library is not None else lib())
+    rc = L.bcc_block_commitments_batch(arr, n, res, device)
+    if rc != 0:
+        raise RuntimeError(f"bcc_block_commitments_batch failed: {rc}")
+    out = []
+    for i in range(n):
+        r = res[i]
+        d = {"status": r.status, "n_tx": r.n_tx, "commit_pos": r.commit_pos,
+             "merkle_root": bytes(r.merkle_root), "witness_root": bytes(r.witness_root)}
+        if txids:
+            buf, cap = bufs[i]
+            written = r.n_tx and cap >= r.n_tx
+            d["txids"] = [buf.raw[32 * k: 32 * k + 32] for k in range(r.n_tx)] if written else None
+            d["txid_buffer"] = buf.raw
+        out.append(d)
+    return out
+
+
+def last_block_stats(library=None):
+    """bcc_last_block_stats: the calling thread's last tx_hashes / merkle_root /
+    block_commitments call."""
+    s = BlockStats()
+    _bind_block(library if library is not None else lib()).bcc_last_block_stats(ctypes.byref(s))
+    return {k: getattr(s, k) for k, _ in BlockStats._fields_}
+
+
+def set_block_round(txs, library=None):
+    """bcc_set_block_round: transactions per device round of the block entries (0: the default)."""
+    _bind_block(library if library is not None else lib()).bcc_set_block_round(txs)
+
+
+def set_host_txhash_blocks(blocks, library=None):
+    """bcc_set_host_txhash_blocks: transactions whose digests need more 64-byte SHA-256 blocks are
+    hashed on the host while the kernel runs (0: none)."""
+    _bind_block(library if library is not None else lib()).bcc_set_host_txhash_blocks(blocks)
+
+
+def block_last_timing_ms(library=None):
+    """bcc_block_last_timing_ms: where the calling thread's last block-entry call on one device
+    spent its time, in ms.  txh_kernel, merkle_kernels, upload, download are event times (zeros
+    unless BCC_BLOCK_TIMING=1 was set when the library was loaded); parse and stage are host
+    clocks."""
+    ms = (ctypes.c_double * 6)()
+    _bind_block(library if library is not None else lib()).bcc_block_last_timing_ms(ms)
+    return dict(zip(("txh_kernel", "merkle_kernels", "upload", "download", "parse", "stage"), ms))
+
+
 def xonly_tweak_check_tuples(tweaked32, parity, internal32, tweak32, device=0):
     """The curve half of the commitment check as a tuple ABI: n rows as concatenated byte strings
     (tweaked key q, one parity byte, internal key p, tweak t) -> bytes of verdicts.  Row semantics

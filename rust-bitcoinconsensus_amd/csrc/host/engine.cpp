@@ -2274,6 +2274,7 @@ void bcc_release_thread_state(void) {
     for (auto& c : tl_chunk) c = ChunkRun();
     bcc::host::inputs_release_thread_state();
     bcc::host::taproot_release_thread_state();
+    bcc::host::block_release_thread_state();
     bcc::release_device_thread_state();
     bcc::release_tuple_thread_state();
     bcc::host::release_pubkey_rows();
@@ -2283,6 +2284,7 @@ void bcc_release_thread_state(void) {
     if (bcc::host::other_active_callers() == 0) {
         bcc::host::run_on_all_workers([] {
             bcc::host::taproot_release_thread_state();
+            bcc::host::block_release_thread_state();
             bcc::release_device_thread_state();
             bcc::release_tuple_thread_state();
             bcc::host::release_pubkey_rows();

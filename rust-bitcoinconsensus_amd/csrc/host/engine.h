@@ -60,6 +60,8 @@ int resilient_round(int dev, const SighashJobs* const* pj, const TupleRows* cons
 
 // Frees the calling thread's Taproot job buffers (host/taproot.cpp).
 void taproot_release_thread_state();
+// Frees the calling thread's block rounds and parsed blocks (host/block.cpp).
+void block_release_thread_state();
 
 // The SigMsg digests of a part's device-built Taproot jobs computed on the host (taproot_host.cpp:
 // the CPU twin of sighash.hip taproot_tx_kernel + taproot_msg_kernel, which taproot_round.hip

@@ -523,6 +523,29 @@ inline void rebase(TapJob& j, const TapBase& b) {
     j.row += b.row;
     j.ext_off += b.ext;
 }
+// Transaction hashing (block_hash.hip tx_hash_kernel, host/block.cpp): one record per uploaded
+// transaction.  A part (one block, or one thread's share of bcc_tx_hashes_batch's items) counts
+// its bytes and rows from zero; BlockBase places it in the round.
+struct BlockBase {
+    uint32_t raw;  // byte in the round's raw blob
+    uint32_t row;  // transaction row
+};
+enum : uint32_t {
+    TXH_HOST = 1,   // a long chain: the host hashes it while the kernel runs (no lane)
+    TXH_W = 2,      // the wtxid row is wanted
+    TXH_WZERO = 4,  // ... as zeros: a coinbase as leaf 0 of its block's witness tree
+};
+struct TxHashJob {
+    uint32_t off, len;  // the whole transaction, witnesses included, in the raw blob
+    uint32_t wit;       // its first witness byte (the end of the outputs); 0: no witness data
+    uint32_t row;       // txid at 32 * row of the txid rows, wtxid at 32 * row of the wtxid rows
+    uint32_t flags;     // TXH_*
+};
+inline void rebase(TxHashJob& j, const BlockBase& b) {  // (wit is tx-relative)
+    j.off += b.raw;
+    j.row += b.row;
+}
+
 struct TaprootTxJobs {
     std::vector<uint8_t> txraw, ext;
     std::vector<TtxRec> ttx;
