@@ -55,15 +55,17 @@ BCC_HD u32 digit_index(u32 l0, u32 l1, u32 l2, u32 l3, int pos, int w, int top, 
     return positive ? (v & mask) : (~v & mask);
 }
 
-// Per-lane Q table: entry i holds x, beta*x, y of (2i+1)Q on the shared-Z curve E'.
+// Per-lane Q table: entry i holds x, beta*x, y and -y of (2i+1)Q on the shared-Z curve E'
+// (fields 0..3).  The ladders read a signed digit's point +-(x, y) or +-(beta*x, y) with
+// get_pair: the sign picks the stored y or -y, so no addition negates.
 // Host version: a plain array (device version lives in ecdsa_verify.hip).
 struct QTableArray {
-    fe e[QTAB][3];
+    fe e[QTAB][4];
     BCC_HD void put(int i, int f, const fe& a) { e[i][f] = a; }
     BCC_HD void get(int i, int f, fe& a) const { a = e[i][f]; }
-    BCC_HD void get_pair(int i, int which, fe& x, fe& y) const {
+    BCC_HD void get_pair(int i, int which, bool neg, fe& x, fe& y) const {
         x = e[i][which];
-        y = e[i][2];
+        y = e[i][neg ? 3 : 2];
     }
 };
 
@@ -102,13 +104,32 @@ BCC_HD void acc_add(gej& acc, bool& inf, const fe& px, const fe& py, const fe& s
     inf = rinf;
 }
 
+// acc += (px, py), the accumulator in extended Jacobian coordinates (the comb: additions only);
+// acc == infinity takes the point as it is.
+BCC_HD void acc_add_xz(gexz& acc, bool& inf, const fe& px, const fe& py) {
+    if (inf) {  // rare: only after an adversarial cancellation
+        acc.x = px;
+        acc.y = py;
+        acc.zz = fe_one();
+        acc.zzz = fe_one();
+        inf = false;
+        return;
+    }
+    gexz r;
+    bool rinf;
+    gexz_add_ge(r, rinf, acc, px, py);
+    acc = r;
+    inf = rinf;
+}
+
 // TwistState::flags bits (ecdsa_twist.h): valid, negated GLV halves, odd-fix corrections
 enum : u32 {
     LS_VALID = 1u, LS_NEG0 = 2u, LS_NEG1 = 4u, LS_CORR0 = 8u,  // LS_CORR0 << slot
 };
 
 // Q table: odd multiples {1,3,..,15}Q on E' with one shared Z (ecmult_odd_multiples_table +
-// ge_globalz_set_table_gej restated, ecmult_impl.h:85-143), plus the lambda images beta*x; returns
+// ge_globalz_set_table_gej restated, ecmult_impl.h:85-143), plus the lambda images beta*x and the
+// negated y (the sign of a digit is a choice between two stored values, not a negation); returns
 // sigma, the scale of E' (total Z of the table).  Built by co-Z arithmetic (Meloni's ZADDU; DBLU
 // for the first doubling): every T_i = T_{i-1} + 2Q is one co-Z addition that also re-expresses
 // 2Q with T_i's Z (4M + 2S instead of a mixed addition's 8M + 3S); the Z ratios
@@ -176,11 +197,13 @@ BCC_HD void build_q_table_coz(const fe& qx, const fe& qy, QT& qt, fe& sigma) {
             fe_mul(ex, ex, f2);
             fe_mul(ey, ey, f3);
         }
-        fe bx;
+        fe bx, ny;
         fe_mul(bx, ex, beta);
+        fe_neg(ny, ey);
         qt.put(i, 0, ex);
         qt.put(i, 1, bx);
         qt.put(i, 2, ey);
+        qt.put(i, 3, ny);
         if (i > 0) fe_mul(f, f, h);
     }
     fe y2;

@@ -213,24 +213,29 @@ BCC_HD bool twist_prep_lane(u32 tag, const fe& px, const fe& py, const sc& r_in,
 }
 
 // B = u2 Q_w: Strauss over the two GLV halves with shared doublings (the Q slots of
-// ladder_accumulate), then the odd-fix corrections.  acc on E_w scaled by sigma; returns inf.
+// ladder_accumulate), then the odd-fix corrections.  The two top digits are table points with
+// Z = 1, so their sum is the affine + affine addition (4M + 2S); every later digit is a mixed
+// addition whose point comes from the table with its sign (get_pair: y or the stored -y).
+// acc on E_w scaled by sigma; returns inf.
 template <class ST, class QT>
 BCC_HD bool twist_accumulate_q(const ST& st, const QT& qt, gej& acc) {
     const bool neg0 = (st.flags & LS_NEG0) != 0, neg1 = (st.flags & LS_NEG1) != 0;
     const fe one = fe_one();
     bool inf = false;
     {
-        bool ng;
+        bool ng;  // the top digits are positive: the sign is the half's
+        fe ax, ay, bx, by;
         u32 idx = digit_index(st.kword(0, 0), st.kword(0, 1), st.kword(0, 2), st.kword(0, 3), TOPQ,
                               WQ, TOPQ, ng);
-        qt.get((int)idx, 0, acc.x);
-        qt.get((int)idx, 2, acc.y);
-        if (neg0) fe_neg(acc.y, acc.y);
-        acc.z = one;
+        qt.get_pair((int)idx, 0, neg0, ax, ay);
+        idx = digit_index(st.kword(1, 0), st.kword(1, 1), st.kword(1, 2), st.kword(1, 3), TOPQ, WQ,
+                          TOPQ, ng);
+        qt.get_pair((int)idx, 1, neg1, bx, by);
+        gej_add_affine(acc, inf, ax, ay, bx, by);
     }
 #pragma unroll 1
-    for (int pos = TOPQ; pos >= -1; pos--) {
-        if (pos >= 0 && pos != TOPQ && !inf) {
+    for (int pos = TOPQ - 1; pos >= -1; pos--) {
+        if (pos >= 0 && !inf) {
             gej t;
             gej_double(t, acc);
             acc = t;
@@ -242,7 +247,6 @@ BCC_HD bool twist_accumulate_q(const ST& st, const QT& qt, gej& acc) {
             u32 idx;
             bool sneg;
             if (pos >= 0) {
-                if (slot == 0 && pos == TOPQ) continue;  // initial value
                 bool dneg;
                 idx = digit_index(st.kword(slot, 0), st.kword(slot, 1), st.kword(slot, 2),
                                   st.kword(slot, 3), pos, WQ, TOPQ, dneg);
@@ -253,8 +257,7 @@ BCC_HD bool twist_accumulate_q(const ST& st, const QT& qt, gej& acc) {
                 sneg = !kneg;
             }
             fe px, py;
-            qt.get_pair((int)idx, slot, px, py);  // (x or beta*x, y)
-            if (sneg) fe_neg(py, py);
+            qt.get_pair((int)idx, slot, sneg, px, py);  // +-(x or beta*x, y)
             acc_add(acc, inf, px, py, one, false);
         }
     }
@@ -274,8 +277,7 @@ BCC_HD bool twist_accumulate_q_half(const ST& st, const QT& qt, gej& acc, int sl
         bool ng;
         const u32 idx = digit_index(st.kword(slot, 0), st.kword(slot, 1), st.kword(slot, 2),
                                     st.kword(slot, 3), TOPQ, WQ, TOPQ, ng);
-        qt.get_pair((int)idx, slot, acc.x, acc.y);
-        if (kneg) fe_neg(acc.y, acc.y);
+        qt.get_pair((int)idx, slot, kneg, acc.x, acc.y);
         acc.z = one;
     }
 #pragma unroll 1
@@ -299,26 +301,30 @@ BCC_HD bool twist_accumulate_q_half(const ST& st, const QT& qt, gej& acc, int sl
             sneg = !kneg;
         }
         fe px, py;
-        qt.get_pair((int)idx, slot, px, py);
-        if (sneg) fe_neg(py, py);
+        qt.get_pair((int)idx, slot, sneg, px, py);
         acc_add(acc, inf, px, py, one, false);
     }
     return inf;
 }
 
-// A = u1 G on E by the fixed-base comb: one addition per window, no doublings.  Returns inf.
+// A = u1 G on E by the fixed-base comb: one addition per window, no doublings.  The two top
+// windows' points are affine, so their sum is the affine + affine addition.  Returns inf.
 template <class ST, class GC>
 BCC_HD bool twist_accumulate_g(const ST& st, const GC& gc, gej& acc) {
     const fe one = fe_one();
     bool inf = false;
     {
-        bool ng;
+        bool ng, neg;
+        fe ax, ay, bx, by;
         u32 idx = comb_digit(st, WC * CTOP, ng);
-        gc.get(CTOP, (int)idx, acc.x, acc.y);
-        acc.z = one;
+        gc.get(CTOP, (int)idx, ax, ay);
+        idx = comb_digit(st, WC * (CTOP - 1), neg);
+        gc.get(CTOP - 1, (int)idx, bx, by);
+        if (neg) fe_neg(by, by);
+        gej_add_affine(acc, inf, ax, ay, bx, by);
     }
 #pragma unroll 1
-    for (int win = CTOP - 1; win >= 0; win--) {
+    for (int win = CTOP - 2; win >= 0; win--) {
         bool neg;
         u32 idx = comb_digit(st, WC * win, neg);
         fe px, py;
@@ -331,18 +337,48 @@ BCC_HD bool twist_accumulate_g(const ST& st, const GC& gc, gej& acc) {
     return inf;
 }
 
-// The w-free final quantities of A + B (see the header).  A on E, B on E_w scaled by sigma.
+// The same comb with the accumulator in extended Jacobian coordinates (the signature ladders: the
+// combine wants Z1^2 and Z1^3, never Z1): 8M + 2S per window instead of 8M + 3S.  The same X and
+// Y as twist_accumulate_g, ZZ = Z^2, ZZZ = Z^3.  Returns inf.
+template <class ST, class GC>
+BCC_HD bool twist_accumulate_g_xz(const ST& st, const GC& gc, gexz& acc) {
+    bool inf = false;
+    {
+        bool ng, neg;
+        fe ax, ay, bx, by;
+        u32 idx = comb_digit(st, WC * CTOP, ng);
+        gc.get(CTOP, (int)idx, ax, ay);
+        idx = comb_digit(st, WC * (CTOP - 1), neg);
+        gc.get(CTOP - 1, (int)idx, bx, by);
+        if (neg) fe_neg(by, by);
+        gexz_add_affine(acc, inf, ax, ay, bx, by);
+    }
+#pragma unroll 1
+    for (int win = CTOP - 2; win >= 0; win--) {
+        bool neg;
+        u32 idx = comb_digit(st, WC * win, neg);
+        fe px, py;
+        gc.get(win, (int)idx, px, py);
+        if (neg) fe_neg(py, py);
+        acc_add_xz(acc, inf, px, py);
+    }
+    if (st.flags & LS_NEGU1) fe_neg(acc.y, acc.y);
+    if (st.flags & LS_U1ZERO) inf = true;
+    return inf;
+}
+
+// The w-free final quantities of A + B (see the header).  A on E with Z1^2 = A.zz and
+// Z1^3 = A.zzz, B on E_w scaled by sigma.
 // Returns false for the exceptional configurations (x(A) == x(B), beta == 0).
-BCC_HD bool twist_combine(const gej& A, const gej& B, const fe& sigma, const fe& v, const sc& r,
+BCC_HD bool twist_combine(const gexz& A, const gej& B, const fe& sigma, const fe& v, const sc& r,
                           fe& al, fe& be, fe& K) {
     // ordered so that A and B die early (the ladder kernel runs at <= 128 VGPRs)
-    fe zb, zb2, z12, u1, u2, s1, s2, h, hh, t;
+    fe zb, zb2, u1, u2, s1, s2, h, hh, t;
+    const fe& z12 = A.zz;
     fe_mul(zb, B.z, sigma);
     fe_sqr(zb2, zb);
-    fe_sqr(z12, A.z);
     fe_mul(u2, B.x, z12);          // U2 = X2 Z1^2
-    fe_mul(t, z12, A.z);
-    fe_mul(s2, B.y, t);            // S2 = Y2 Z1^3
+    fe_mul(s2, B.y, A.zzz);        // S2 = Y2 Z1^3
     fe_mul(t, A.y, zb2);
     fe_mul(t, t, zb);
     fe_mul(s1, t, v);              // S1 = w s1, s1 = Y1 Zb^3 v
@@ -477,6 +513,14 @@ BCC_HD int twist_exceptional(const gej& A, bool ainf, const gej& B, bool binf, c
     return fe_equal(lhs, R.x) ? 1 : 0;
 }
 
+// ... with A as the comb leaves it (extended Jacobian): the same point with Z = ZZZ.
+BCC_HD int twist_exceptional(const gexz& A, bool ainf, const gej& B, bool binf, const fe& sigma,
+                             const fe& v, const fe& ychk, u32 flags, const sc& r) {
+    gej a;
+    gexz_to_gej(a, A);
+    return twist_exceptional(a, ainf, B, binf, sigma, v, ychk, flags, r);
+}
+
 // Status of a lane after the twist ladder.
 enum : u32 { TW_REJECT = 0, TW_NORMAL = 1, TW_EXCEPT = 2 };
 
@@ -487,9 +531,10 @@ BCC_HD int ecdsa_verify_twist_lane(u32 tag, const fe& px, const fe& py, const sc
                                    const sc& s, const sc& m, QT& qt, const GC& gc) {
     TwistState st;
     if (!twist_prep_lane(tag, px, py, r, s, m, nullptr, qt, st)) return 0;
-    gej A, B;
+    gexz A;
+    gej B;
     const bool binf = twist_accumulate_q(st, qt, B);
-    const bool ainf = twist_accumulate_g(st, gc, A);
+    const bool ainf = twist_accumulate_g_xz(st, gc, A);
     fe al, be, K;
     if (binf || ainf || !twist_combine(A, B, st.sigma, st.v, st.r, al, be, K))
         return twist_exceptional(A, ainf, B, binf, st.sigma, st.v, st.ychk, st.flags, st.r);
@@ -550,8 +595,7 @@ inline bool twist_accumulate_q_wnaf(const ST& st, const u32 (&k1)[4], const u32 
             const int v = i < (slot ? n1 : n0) ? d[slot][i] : 0;
             if (v == 0) continue;
             fe px, py;
-            qt.get_pair((v < 0 ? -v : v) >> 1, slot, px, py);  // (|v| - 1) / 2 for odd |v|
-            if ((v < 0) != kneg[slot]) fe_neg(py, py);
+            qt.get_pair((v < 0 ? -v : v) >> 1, slot, (v < 0) != kneg[slot], px, py);  // (|v| - 1) / 2
             acc_add(acc, inf, px, py, one, false);
         }
     }
@@ -576,9 +620,10 @@ inline int ecdsa_verify_twist_host(u32 tag, const fe& px, const fe& py, const sc
     if (st.flags & LS_CORR0) k1[0] &= ~1u;
     if (st.flags & (LS_CORR0 << 1)) k2[0] &= ~1u;
     twist_prep_u1(m, sinv, &st.flags, st.k[2], st.k[3]);
-    gej A, B;
+    gexz A;
+    gej B;
     const bool binf = twist_accumulate_q_wnaf(st, k1, k2, qt, B);
-    const bool ainf = twist_accumulate_g(st, gc, A);
+    const bool ainf = twist_accumulate_g_xz(st, gc, A);
     fe al, be, K;
     if (binf || ainf || !twist_combine(A, B, st.sigma, st.v, st.r, al, be, K))
         return twist_exceptional(A, ainf, B, binf, st.sigma, st.v, st.ychk, st.flags, st.r);
@@ -761,7 +806,7 @@ BCC_HD int schnorr_verify_twist_lane(const fe& px, const fe& rx, const sc& s, co
                                      QT& qt, const GC& gc) {
     TwistState st;
     if (!schnorr_twist_prep(px, rx, s, m, qt, st)) return 0;
-    gej A, B;
+    gej A, B;  // the Jacobian comb: schnorr_twist_combine wants Z1 itself
     const bool binf = twist_accumulate_q(st, qt, B);
     const bool ainf = twist_accumulate_g(st, gc, A);
     fe al, be, dd, c0, c1;

@@ -8,12 +8,16 @@
 //                                      tuples (3 mults/tuple + one safegcd inversion per thread)
 //   K_copy    keyq_copy_kernel         only with early twins: their key half and parked B copied
 //   K_keyq    twist_keyq_kernel        key parse without a square root, v = x^3 + 7, Q_w = (x v, v^2),
-//                                      co-Z Q_w table, r / s checks, u2 = r s^-1, GLV split,
-//                                      B = u2 Q_w.  Two launches when the round is not a whole number
+//                                      co-Z Q_w table (entries x | y | beta x | -y: a digit's sign
+//                                      is a choice of y, never a negation), r / s checks,
+//                                      u2 = r s^-1, GLV split, B = u2 Q_w (the two top digits by an
+//                                      affine + affine addition).  Two launches when the round is not a whole number
 //                                      of residency rounds; twist_keyq2_kernel (two lanes per tuple)
 //                                      for a round of at most one wave per SIMD
-//   K_tladder_g twist_ladder_g_kernel  u1 = m s^-1, A = u1 G (fixed-base comb from HBM tables), the
-//                                      combine, alpha / beta / K of the x-test
+//   K_tladder_g twist_ladder_g_kernel  u1 = m s^-1, A = u1 G (fixed-base comb from HBM tables, the
+//                                      accumulator in extended Jacobian coordinates X, Y, ZZ, ZZZ:
+//                                      8M + 2S per window), the combine on ZZ and ZZZ, alpha /
+//                                      beta / K of the x-test
 //   K_tfin    twist_fin_kernel<false>  batched beta^-1, "gamma = -alpha / beta is the key's y",
 //                                      exact fallback for the exceptional lanes
 // ECDSA, chunked path (a round above the scratch chunk): K_inv once, then per chunk
@@ -44,6 +48,7 @@
 #include <cstdlib>
 #include <memory>
 #include <string>
+#include <type_traits>
 
 #include "bcc_amd.h"
 #include "ecdsa_lane.h"
@@ -70,24 +75,20 @@ __device__ __forceinline__ const u32* lane_words(const u32* base, size_t t, int 
 }
 
 // Per-lane Q table, lane-major: lane t's 1 KiB table is contiguous at base + t * QTABLE_WORDS,
-// entry i at 32 words [x | y | beta*x | y] (y stored twice), so an addition reads its point
-// (x, y) or (beta*x, y) as one aligned 64-byte piece with four 16-byte loads.  The ladder gathers
+// entry i at 32 words [x | y | beta*x | -y], so an addition reads its signed point +-(x, y) or
+// +-(beta*x, y) as two aligned 32-byte pieces of one 128-byte line with four 16-byte loads, and
+// never negates.  The ladder gathers
 // by a per-lane digit index: with the entry words interleaved across lanes instead (word-major),
 // each of those loads hit up to 8 table rows per wave and the L2 fetched ~3.7x the bytes used
 // (rocprofv3 TCP_TCC_READ_REQ / SQ_INSTS_VMEM_RD = 14.7, 90 % L2 misses, profiles/r01g_pmc).
-// Fields for put / get: 0 = x, 1 = beta*x (an H value while the table is built), 2 = y.
+// Fields for put / get: 0 = x, 1 = beta*x (an H value while the table is built), 2 = y, 3 = -y.
 struct QTableGlobal {
     u32* base;
-    __device__ static int field_off(int f) { return f == 0 ? 0 : f == 1 ? 16 : 8; }
+    __device__ static int field_off(int f) { return f == 0 ? 0 : f == 1 ? 16 : f == 2 ? 8 : 24; }
     __device__ void put(int i, int f, const fe& a) {
         uint4* p = reinterpret_cast<uint4*>(base + i * 32 + field_off(f));
         p[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
         p[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-        if (f == 2) {
-            uint4* q = reinterpret_cast<uint4*>(base + i * 32 + 24);
-            q[0] = p[0];
-            q[1] = p[1];
-        }
     }
     __device__ void get(int i, int f, fe& a) const {
         const uint4* p = reinterpret_cast<const uint4*>(base + i * 32 + field_off(f));
@@ -95,10 +96,11 @@ struct QTableGlobal {
         a.v[0] = u.x; a.v[1] = u.y; a.v[2] = u.z; a.v[3] = u.w;
         a.v[4] = v.x; a.v[5] = v.y; a.v[6] = v.z; a.v[7] = v.w;
     }
-    // (x, y) for which == 0, (beta*x, y) for which == 1: one 64-byte piece
-    __device__ void get_pair(int i, int which, fe& x, fe& y) const {
+    // x for which == 0, beta*x for which == 1; y, or -y for neg: two 32-byte pieces of one line
+    __device__ void get_pair(int i, int which, bool neg, fe& x, fe& y) const {
         const uint4* p = reinterpret_cast<const uint4*>(base + i * 32 + 16 * which);
-        const uint4 a = p[0], b = p[1], c = p[2], d = p[3];
+        const uint4* q = reinterpret_cast<const uint4*>(base + i * 32 + (neg ? 24 : 8));
+        const uint4 a = p[0], b = p[1], c = q[0], d = q[1];
         x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
         x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
         y.v[0] = c.x; y.v[1] = c.y; y.v[2] = c.z; y.v[3] = c.w;
@@ -326,12 +328,18 @@ __device__ __forceinline__ void twist_q_part(u32* lt, const TwistStateView& st) 
 }
 
 // The G half: A = u1 G by the comb, B back from the table, the w-free combine; writes the lane's
-// status (and alpha / beta / K, or the parked A for the exact fallback).
+// status (and alpha / beta / K, or the parked A for the exact fallback).  The ECDSA comb runs in
+// extended Jacobian coordinates (its combine reads Z1^2 and Z1^3); BIP340's combine wants Z1 for
+// Dd, and the wider accumulator cost schnorr_tladder_kernel 24 bytes of scratch more, so it keeps
+// the Jacobian comb.
 template <bool BIP340>
 __device__ __forceinline__ void twist_g_part(u32* w, u32* lt, const u32* gcomb, TwistStateView& st) {
     u32 stat = TW_NORMAL;
-    gej A, B;
-    const bool ainf = twist_accumulate_g(st, GCombGlobal{gcomb}, A);
+    typename std::conditional<BIP340, gej, gexz>::type A;
+    gej B;
+    bool ainf;
+    if constexpr (BIP340) ainf = twist_accumulate_g(st, GCombGlobal{gcomb}, A);
+    else ainf = twist_accumulate_g_xz(st, GCombGlobal{gcomb}, A);
     const bool binf = unpark_gej(lt + PARK_B, B);
     fe v, al, be, K;
     sc r;
@@ -351,7 +359,13 @@ __device__ __forceinline__ void twist_g_part(u32* w, u32* lt, const u32* gcomb, 
         ok = !binf && !ainf && twist_combine(A, B, st.sigma, v, r, al, be, K);
     }
     if (!ok) {
-        park_gej(lt + PARK_A, A, ainf);
+        if constexpr (BIP340) {
+            park_gej(lt + PARK_A, A, ainf);
+        } else {
+            gej a;  // the fallback adds Jacobian points
+            gexz_to_gej(a, A);
+            park_gej(lt + PARK_A, a, ainf);
+        }
         stat = TW_EXCEPT;
     } else {
         tw_store(w, T_AL, al.v);

@@ -908,4 +908,140 @@ BCC_HD void gej_add_zinv(gej& r, bool& inf, const gej& a, const fe& bx, const fe
     inf = false;
 }
 
+// r = a + b, both affine on the same curve: gej_add_zinv with Z1 = 1 and bzinv = 1, where
+// U2 = bx, S2 = by and Z3 = H need no product.  4M + 2S.  The same exceptional cases
+// (a == b -> double, a == -b -> infinity with r = a); the result is the same Jacobian point.
+BCC_HD void gej_add_affine(gej& r, bool& inf, const fe& ax, const fe& ay, const fe& bx,
+                           const fe& by) {
+    fe h, rr, hh, hhh, v, t;
+    fe_sub(h, bx, ax);           // H = x2 - x1
+    fe_sub(rr, by, ay);          // R = y2 - y1
+    if (fe_is_zero(h)) {         // rare, adversarial only
+        gej a;
+        a.x = ax;
+        a.y = ay;
+        a.z = fe_one();
+        if (fe_is_zero(rr)) {
+            gej_double(r, a);
+            inf = false;
+        } else {
+            inf = true;
+            r = a;
+        }
+        return;
+    }
+    fe_sqr(hh, h);               // H^2
+    fe_mul(hhh, h, hh);          // H^3
+    fe_mul(v, ax, hh);           // V = x1*H^2
+    r.z = h;                     // Z3 = H
+    fe_sqr(t, rr);
+    fe_sub(t, t, hhh);
+    fe_sub(t, t, v);
+    fe_sub(r.x, t, v);           // X3 = R^2 - H^3 - 2V
+    fe_sub(t, v, r.x);
+    fe_mul(t, rr, t);
+    fe_mul(hhh, ay, hhh);
+    fe_sub(r.y, t, hhh);         // Y3 = R(V - X3) - y1*H^3
+    inf = false;
+}
+
+// Extended Jacobian coordinates (X, Y, ZZ, ZZZ) with ZZ^3 == ZZZ^2: the point (X / ZZ, Y / ZZZ).
+// An accumulator that is only ever added to (the comb: no doublings) keeps Z^2 and Z^3 instead of
+// Z, so a mixed addition squares nothing but H and R.  For the Jacobian point (X, Y, Z) the same
+// X and Y with ZZ = Z^2, ZZZ = Z^3.
+struct gexz {
+    fe x, y, zz, zzz;
+};
+
+// The Jacobian point (X ZZ^2, Y ZZ^3, ZZZ): the same point with Z' = Z^3 (exceptional paths only).
+BCC_HD void gexz_to_gej(gej& r, const gexz& a) {
+    fe z2, z3;
+    fe_sqr(z2, a.zz);
+    fe_mul(z3, z2, a.zz);
+    fe_mul(r.x, a.x, z2);
+    fe_mul(r.y, a.y, z3);
+    r.z = a.zzz;
+}
+
+BCC_HD void gexz_from_gej(gexz& r, const gej& a) {
+    r.x = a.x;
+    r.y = a.y;
+    fe_sqr(r.zz, a.z);
+    fe_mul(r.zzz, r.zz, a.z);
+}
+
+// gej_add_affine with the result in extended Jacobian coordinates: ZZ3 = H^2 and ZZZ3 = H^3 are
+// already there.  4M + 2S.
+BCC_HD void gexz_add_affine(gexz& r, bool& inf, const fe& ax, const fe& ay, const fe& bx,
+                            const fe& by) {
+    fe h, rr, v, t;
+    fe_sub(h, bx, ax);           // H = x2 - x1
+    fe_sub(rr, by, ay);          // R = y2 - y1
+    if (fe_is_zero(h)) {         // rare, adversarial only
+        gej a, d;
+        a.x = ax;
+        a.y = ay;
+        a.z = fe_one();
+        if (fe_is_zero(rr)) {
+            gej_double(d, a);
+            gexz_from_gej(r, d);
+            inf = false;
+        } else {
+            inf = true;
+            gexz_from_gej(r, a);
+        }
+        return;
+    }
+    fe_sqr(r.zz, h);             // ZZ3 = H^2
+    fe_mul(r.zzz, h, r.zz);      // ZZZ3 = H^3
+    fe_mul(v, ax, r.zz);         // V = x1*H^2
+    fe_sqr(t, rr);
+    fe_sub(t, t, r.zzz);
+    fe_sub(t, t, v);
+    fe_sub(r.x, t, v);           // X3 = R^2 - H^3 - 2V
+    fe_sub(t, v, r.x);
+    fe_mul(t, rr, t);
+    fe_mul(v, ay, r.zzz);
+    fe_sub(r.y, t, v);           // Y3 = R(V - X3) - y1*H^3
+    inf = false;
+}
+
+// r = a + (bx, by), a in extended Jacobian coordinates and not infinity, b affine on the same
+// curve (madd-2008-s): 8M + 2S.  X3 and Y3 are gej_add_zinv's for the Jacobian (X1, Y1, Z1), and
+// ZZ3 = (Z1 H)^2, ZZZ3 = (Z1 H)^3; the same exceptional cases.
+BCC_HD void gexz_add_ge(gexz& r, bool& inf, const gexz& a, const fe& bx, const fe& by) {
+    fe u2, s2, h, rr, hh, hhh, v, t;
+    fe_mul(u2, bx, a.zz);        // U2 = bx*ZZ1
+    fe_mul(s2, by, a.zzz);       // S2 = by*ZZZ1
+    fe_sub(h, u2, a.x);          // H = U2 - X1
+    fe_sub(rr, s2, a.y);         // R = S2 - Y1
+    if (fe_is_zero(h)) {         // rare, adversarial only
+        if (fe_is_zero(rr)) {
+            gej j, d;
+            gexz_to_gej(j, a);
+            gej_double(d, j);
+            gexz_from_gej(r, d);
+            inf = false;
+        } else {
+            inf = true;
+            r = a;
+        }
+        return;
+    }
+    fe_sqr(hh, h);               // H^2
+    fe_mul(hhh, h, hh);          // H^3
+    fe_mul(v, a.x, hh);          // V = X1*H^2
+    fe_mul(r.zz, a.zz, hh);      // ZZ3 = ZZ1*H^2
+    fe_mul(r.zzz, a.zzz, hhh);   // ZZZ3 = ZZZ1*H^3
+    fe_sqr(t, rr);
+    fe_sub(t, t, hhh);
+    fe_sub(t, t, v);
+    fe_sub(r.x, t, v);           // X3 = R^2 - H^3 - 2V
+    fe_sub(t, v, r.x);
+    fe_mul(t, rr, t);
+    fe_mul(hhh, a.y, hhh);
+    fe_sub(r.y, t, hhh);         // Y3 = R(V - X3) - Y1*H^3
+    inf = false;
+}
+
 }  // namespace bcc
