@@ -365,6 +365,84 @@ int bcc_set_host_txhash_blocks(unsigned blocks);
  * page-locked image of the upload).  For tools/block_bench.py. */
 void bcc_block_last_timing_ms(double* ms6);
 
+/* ---- header chains: block hashes, proof of work, retargets ----------------------------------------
+ * What CheckBlockHeader and ContextualCheckBlockHeader decide for a run of consecutive 80-byte
+ * headers (validation.cpp:3341-3350, 3496-3535): the block hash (SHA-256d of the header),
+ * CheckProofOfWork (pow.cpp:74-91), the link to the header before, the expected nBits
+ * (GetNextWorkRequired / CalculateNextWorkRequired, pow.cpp:13-72, arith_uint256.cpp:203-244), the
+ * median time past of the 11 blocks before (chain.h:257-275), the caller's upper time bound and the
+ * three version gates; and the chain's work (GetBlockProof, chain.cpp:122-135).  Hashes are raw
+ * digest bytes, as in the block entries above.  One SHA-256d lane per header, then one context lane
+ * per header, on the GPU. */
+typedef struct bcc_header_params {          /* Consensus::Params, the fields the header rules read */
+    unsigned char pow_limit[32];            /* uint256 bytes, as uint256::begin() orders them */
+    int64_t pow_target_timespan, pow_target_spacing; /* both > 0, interval = timespan / spacing >= 1,
+                                               timespan < 2^30 (the retarget's factors are 32-bit) */
+    int pow_no_retargeting;                 /* fPowNoRetargeting */
+    int pow_allow_min_difficulty;           /* must be 0: the testnet exception is not implemented */
+    int bip34_height, bip66_height, bip65_height;
+} bcc_header_params;
+typedef struct bcc_header_anchor {          /* the block headers[0] builds on */
+    int height;                             /* >= 0; headers[0] has height + 1 */
+    unsigned char hash[32];
+    uint32_t bits;
+    uint32_t times[11]; unsigned n_times;   /* nTime of the anchor and its ancestors, newest first:
+                                               min(11, height + 1) of them, at least the anchor's */
+    uint32_t period_first_time;             /* nTime of the first block of the retarget period the
+                                               next boundary closes (the block `interval` below that
+                                               boundary, which may be the anchor itself); ignored
+                                               with pow_no_retargeting */
+} bcc_header_anchor;
+#define BCC_HEADER_OK 0
+#define BCC_HEADER_HIGH_HASH 1        /* CheckProofOfWork false: "high-hash" */
+#define BCC_HEADER_PREV_MISMATCH 2    /* hashPrevBlock != hash of the header before it / the anchor */
+#define BCC_HEADER_BAD_DIFFBITS 3     /* "bad-diffbits" */
+#define BCC_HEADER_TIME_TOO_OLD 4     /* nTime <= median time past of the 11 before it */
+#define BCC_HEADER_TIME_TOO_NEW 5     /* nTime > max_time; max_time 0: rule off */
+#define BCC_HEADER_BAD_VERSION 6      /* "bad-version" */
+/* status_out[i] (required): the first rule header i breaks, in the order above.  Header i is judged
+ * against the header bytes before it as given, whether or not those headers passed.  anchor NULL:
+ * headers[0] is a genesis of height 0 and gets the proof-of-work rule only.  nTime is widened
+ * unsigned, nVersion is signed.  hash_out (optional, 32 bytes per header): every header's hash.
+ * chain_work_out (optional): the sum of GetBlockProof over the headers before the first one whose
+ * status is not OK, as a little-endian 256-bit number; the anchor's work is not in it.  Returns the
+ * index of that first header, n when every status is OK (0 for n == 0), or -1: a null headers80,
+ * params or status_out, parameters outside the ranges above, an anchor with a negative height or
+ * n_times outside 1..11, heights past 2^31 - 1, or a device failure under BCC_DEVICE_FAILURE_ERROR
+ * (no output is meaningful then).  Synchronous on `device`; -1 spreads contiguous ranges over the
+ * bcc_set_devices() GPUs.  A round is at most bcc_set_header_round() headers, uploaded in one copy
+ * with what its first headers need from before it (the last hash and bits, eleven times, the
+ * period's first time), which the host reads from the header bytes themselves.  Rounds of at most
+ * the entry's small-round threshold (128 headers, measured: DESIGN.md 3.18), and rounds the device
+ * could not deliver after one retry, run the same lane code on the host;
+ * bcc_set_host_small_round() and the failure rules apply as they do to the block entries, and
+ * bcc_debug_fail_device_rounds[_code] reaches these rounds too.  Results never depend on the device
+ * set, the round cut, the thread count or any threshold. */
+long bcc_headers_batch(const unsigned char* headers80, size_t n, const bcc_header_params* params,
+                       const bcc_header_anchor* anchor, int64_t max_time, unsigned char* hash_out,
+                       int* status_out, unsigned char* chain_work_out, int device);
+/* The layer below: ok_out[i] = CheckProofOfWork(hash32_i, bits[i]) under pow_limit (32 uint256
+ * bytes), one lane per row.  Returns 0 (also for n == 0), -1 for null arrays, or the HIP error of a
+ * failed round under BCC_DEVICE_FAILURE_ERROR.  device -1: the first of the bcc_set_devices() GPUs.
+ * Its small-round threshold is 2,048 rows (provisional: not measured). */
+int mi_pow_check_tuples(const unsigned char* hash32, const uint32_t* bits, size_t n,
+                        const unsigned char* pow_limit, unsigned char* ok_out, int device);
+typedef struct bcc_header_stats {
+    size_t headers;                     /* headers (rows of mi_pow_check_tuples) */
+    size_t device_rounds, host_rounds;  /* host_rounds: small rounds + failure fallbacks */
+    size_t device_retries;
+} bcc_header_stats;
+/* Statistics of the calling thread's last bcc_headers_batch / mi_pow_check_tuples call. */
+void bcc_last_header_stats(bcc_header_stats* out);
+/* Headers per device round (0, the default: the engine's choice, 262,144).  For tests: a small value
+ * puts round cuts inside a small batch.  Returns 0. */
+int bcc_set_header_round(size_t headers);
+/* Event times in milliseconds of the calling thread's last bcc_headers_batch call on one device,
+ * summed over its rounds: ms4[0] header_hash_kernel, ms4[1] header_context_kernel, ms4[2] the
+ * uploads, ms4[3] the downloads.  Zeros unless BCC_HEADER_TIMING=1 was in the environment when the
+ * library was loaded.  For tools/headers_bench.py. */
+void bcc_header_last_timing_ms(double* ms4);
+
 /* Where the Taproot side's work ran. */
 typedef struct bcc_taproot_stats {
     size_t items, checks, commits;   /* signature rows and commitment lanes of the call */

@@ -1154,6 +1154,132 @@ def block_last_timing_ms(library=None):
     return dict(zip(("txh_kernel", "merkle_kernels", "upload", "download", "parse", "stage"), ms))
 
 
+# ---- header chains: block hashes, proof of work, retargets (include/bcc_amd.h) -----------------
+HEADER_OK = 0
+HEADER_HIGH_HASH = 1
+HEADER_PREV_MISMATCH = 2
+HEADER_BAD_DIFFBITS = 3
+HEADER_TIME_TOO_OLD = 4
+HEADER_TIME_TOO_NEW = 5
+HEADER_BAD_VERSION = 6
+
+
+class HeaderParams(ctypes.Structure):
+    """include/bcc_amd.h bcc_header_params.  HeaderParams.make(pow_limit=<int or 32 bytes>, ...)."""
+    _fields_ = [("pow_limit", ctypes.c_ubyte * 32), ("pow_target_timespan", ctypes.c_int64),
+                ("pow_target_spacing", ctypes.c_int64), ("pow_no_retargeting", ctypes.c_int),
+                ("pow_allow_min_difficulty", ctypes.c_int), ("bip34_height", ctypes.c_int),
+                ("bip66_height", ctypes.c_int), ("bip65_height", ctypes.c_int)]
+
+    @classmethod
+    def make(cls, pow_limit, timespan, spacing, no_retargeting=False, allow_min_difficulty=False,
+             bip34=0, bip66=0, bip65=0):
+        raw = pow_limit.to_bytes(32, "little") if isinstance(pow_limit, int) else bytes(pow_limit)
+        assert len(raw) == 32
+        return cls((ctypes.c_ubyte * 32)(*raw), timespan, spacing, int(no_retargeting),
+                   int(allow_min_difficulty), bip34, bip66, bip65)
+
+
+# chainparams.cpp CMainParams: powLimit, two weeks over ten minutes, BIP34 / BIP66 / BIP65 heights
+MAINNET = HeaderParams.make(0xffff << 208, 14 * 24 * 60 * 60, 10 * 60, bip34=227931, bip66=363725,
+                            bip65=388381)
+
+
+class HeaderAnchor(ctypes.Structure):
+    """include/bcc_amd.h bcc_header_anchor.  HeaderAnchor.make(height, hash, bits, times, first)."""
+    _fields_ = [("height", ctypes.c_int), ("hash", ctypes.c_ubyte * 32), ("bits", ctypes.c_uint32),
+                ("times", ctypes.c_uint32 * 11), ("n_times", ctypes.c_uint),
+                ("period_first_time", ctypes.c_uint32)]
+
+    @classmethod
+    def make(cls, height, hash32, bits, times, period_first_time=0):
+        """times: nTime of the anchor and its ancestors, newest first (at most 11 are kept)."""
+        times = list(times)[:11]
+        return cls(height, (ctypes.c_ubyte * 32)(*hash32), bits,
+                   (ctypes.c_uint32 * 11)(*times), len(times), period_first_time)
+
+
+class HeaderStats(ctypes.Structure):
+    """include/bcc_amd.h bcc_header_stats."""
+    _fields_ = [(k, ctypes.c_size_t) for k in ("headers", "device_rounds", "host_rounds",
+                                               "device_retries")]
+
+
+def _bind_headers(L):
+    if getattr(L, "_bcc_headers_bound", False):
+        return L
+    L.bcc_headers_batch.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(HeaderParams),
+                                    ctypes.POINTER(HeaderAnchor), ctypes.c_int64, ctypes.c_void_p,
+                                    ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int]
+    L.bcc_headers_batch.restype = ctypes.c_long
+    L.mi_pow_check_tuples.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+                                      ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int]
+    L.bcc_last_header_stats.argtypes = [ctypes.POINTER(HeaderStats)]
+    L.bcc_last_header_stats.restype = None
+    L.bcc_set_header_round.argtypes = [ctypes.c_size_t]
+    L.bcc_header_last_timing_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.bcc_header_last_timing_ms.restype = None
+    L._bcc_headers_bound = True
+    return L
+
+
+def check_headers(headers, params=MAINNET, anchor=None, max_time=0, device=0, hashes=True,
+                  library=None):
+    """bcc_headers_batch over consecutive 80-byte headers (a list, or their concatenation).
+    anchor: the HeaderAnchor headers[0] builds on, None when headers[0] is a genesis.  Returns a
+    dict: first_invalid (len(headers) when every header passes), status (HEADER_* per header),
+    hashes (raw digest bytes per header; None with hashes=False) and chain_work (the int sum of
+    GetBlockProof over the headers before first_invalid)."""
+    blob = bytes(headers) if isinstance(headers, (bytes, bytearray)) else b"".join(headers)
+    assert len(blob) % 80 == 0
+    n = len(blob) // 80
+    status = (ctypes.c_int * max(n, 1))()
+    hb = ctypes.create_string_buffer(32 * max(n, 1)) if hashes else None
+    work = ctypes.create_string_buffer(32)
+    L = _bind_headers(library if library is not None else lib())
+    rc = L.bcc_headers_batch(blob, n, ctypes.byref(params), ctypes.byref(anchor) if anchor else None,
+                             max_time, hb, status, work, device)
+    if rc < 0:
+        raise RuntimeError(f"bcc_headers_batch failed: {rc}")
+    return {"first_invalid": rc, "status": [status[i] for i in range(n)],
+            "hashes": [hb.raw[32 * i: 32 * i + 32] for i in range(n)] if hashes else None,
+            "chain_work": int.from_bytes(work.raw, "little")}
+
+
+def pow_check_tuples(hash32, bits, pow_limit, device=0, library=None):
+    """mi_pow_check_tuples: CheckProofOfWork per row.  hash32: n raw 32-byte hashes concatenated;
+    bits: n compact targets; pow_limit: an int or 32 uint256 bytes.  Returns n verdict bytes."""
+    n = len(bits)
+    assert len(hash32) == 32 * n
+    limit = pow_limit.to_bytes(32, "little") if isinstance(pow_limit, int) else bytes(pow_limit)
+    out = ctypes.create_string_buffer(max(n, 1))
+    L = _bind_headers(library if library is not None else lib())
+    rc = L.mi_pow_check_tuples(bytes(hash32), (ctypes.c_uint32 * max(n, 1))(*bits), n, limit, out, device)
+    if rc != 0:
+        raise RuntimeError(f"mi_pow_check_tuples failed: {rc}")
+    return out.raw[:n]
+
+
+def last_header_stats(library=None):
+    """bcc_last_header_stats: the calling thread's last check_headers / pow_check_tuples call."""
+    s = HeaderStats()
+    _bind_headers(library if library is not None else lib()).bcc_last_header_stats(ctypes.byref(s))
+    return {k: getattr(s, k) for k, _ in HeaderStats._fields_}
+
+
+def set_header_round(headers, library=None):
+    """bcc_set_header_round: headers per device round of check_headers (0: the default)."""
+    _bind_headers(library if library is not None else lib()).bcc_set_header_round(headers)
+
+
+def header_last_timing_ms(library=None):
+    """bcc_header_last_timing_ms: event times in ms of the calling thread's last check_headers
+    call on one device (zeros unless BCC_HEADER_TIMING=1 was set when the library was loaded)."""
+    ms = (ctypes.c_double * 4)()
+    _bind_headers(library if library is not None else lib()).bcc_header_last_timing_ms(ms)
+    return dict(zip(("hash_kernel", "context_kernel", "upload", "download"), ms))
+
+
 def xonly_tweak_check_tuples(tweaked32, parity, internal32, tweak32, device=0):
     """The curve half of the commitment check as a tuple ABI: n rows as concatenated byte strings
     (tweaked key q, one parity byte, internal key p, tweak t) -> bytes of verdicts.  Row semantics

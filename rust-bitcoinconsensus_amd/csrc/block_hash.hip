@@ -114,37 +114,6 @@ const bool g_timing = [] {
 }();
 thread_local double tl_kernel_ms[KT_KERNELS];
 
-struct KernelTimer {
-    struct Span {
-        hipEvent_t a, b;
-        int k;
-    };
-    std::vector<Span> spans;
-    hipStream_t st = nullptr;
-    void begin(int k) {
-        if (!g_timing) return;
-        Span s{nullptr, nullptr, k};
-        if (hipEventCreate(&s.a) != hipSuccess || hipEventCreate(&s.b) != hipSuccess) return;
-        (void)hipEventRecord(s.a, st);
-        spans.push_back(s);
-    }
-    void end() {
-        if (g_timing && !spans.empty()) (void)hipEventRecord(spans.back().b, st);
-    }
-    void collect() {  // after the stream has been synchronised
-        for (Span& s : spans) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) tl_kernel_ms[s.k] += ms;
-        }
-    }
-    ~KernelTimer() {
-        for (Span& s : spans) {
-            (void)hipEventDestroy(s.a);
-            (void)hipEventDestroy(s.b);
-        }
-    }
-};
-
 // what the calling thread keeps between rounds
 struct RoundTables {
     std::vector<uint32_t> lanes, late, level, level_lanes;
@@ -216,8 +185,7 @@ int block_round(int device, BlockRound& r) {
     tl_kernel_ms[BLOCK_MS_STAGE] +=
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - stage0).count();
 
-    KernelTimer kt;
-    kt.st = st;
+    EventSpans kt(g_timing, tl_kernel_ms, st);
     uint8_t* d_nodes = d + off[NODES];
     kt.begin(KT_UP);
     if (off[UPLOADED]) BCC_HIP_TRY(hipMemcpyAsync(d, h, off[UPLOADED], hipMemcpyHostToDevice, st));
