@@ -365,6 +365,96 @@ int bcc_set_host_txhash_blocks(unsigned blocks);
  * page-locked image of the upload).  For tools/block_bench.py. */
 void bcc_block_last_timing_ms(double* ms6);
 
+/* ---- a block's transaction rules, sigops, finality, coinbase height and sizes ---------------------
+ * The rest of CheckBlock and ContextualCheckBlock (validation.cpp:3387-3416, 3543-3620) that needs
+ * no UTXO: CheckTransaction for every transaction (consensus/tx_check.cpp:10-58, the duplicate-input
+ * rule included), GetLegacySigOpCount and IsFinalTx (consensus/tx_verify.cpp:17-28, 107-119), the
+ * coinbase position, the BIP34 height prefix, the stripped size and the weight.  The transactions
+ * are the ones a block round has uploaded for hashing: one lane per transaction walks its inputs and
+ * outputs, one lane per input of a transaction with two or more inputs probes a hash table of
+ * outpoints, one wave per block reduces the records; one record per block comes back.  The
+ * conventions are the block entries' above (synchronous, device == -1, null arguments, the host
+ * route for small rounds, long transactions and device failures, results independent of every
+ * setting); bcc_last_block_stats and bcc_block_last_timing_ms describe these entries too.
+ *
+ * Out of scope, the caller's: the UTXO-dependent rules (CheckTxInputs, P2SH and witness sigop cost,
+ * BIP68, BIP30, a double spend between two transactions of a block), and deciding the lock-time
+ * cutoff and the activation flags. */
+#define BCC_TX_OK 0
+#define BCC_TX_ERR_VIN_EMPTY 16            /* "bad-txns-vin-empty" */
+#define BCC_TX_ERR_VOUT_EMPTY 17           /* "bad-txns-vout-empty" */
+#define BCC_TX_ERR_OVERSIZE 18             /* "bad-txns-oversize": stripped size * 4 > 4,000,000 */
+#define BCC_TX_ERR_VOUT_NEGATIVE 19        /* "bad-txns-vout-negative" */
+#define BCC_TX_ERR_VOUT_TOOLARGE 20        /* "bad-txns-vout-toolarge" */
+#define BCC_TX_ERR_TXOUTTOTAL_TOOLARGE 21  /* "bad-txns-txouttotal-toolarge" */
+#define BCC_TX_ERR_INPUTS_DUPLICATE 22     /* "bad-txns-inputs-duplicate" (CVE-2018-17144) */
+#define BCC_TX_ERR_CB_LENGTH 23            /* "bad-cb-length" */
+#define BCC_TX_ERR_PREVOUT_NULL 24         /* "bad-txns-prevout-null" */
+typedef struct bcc_tx_check_result {
+    int status;                  /* BCC_TX_OK, a BCC_TX_ERR_* above (the first in CheckTransaction's
+                                    order), or bitcoinconsensus_ERR_TX_DESERIALIZE /
+                                    ERR_TX_SIZE_MISMATCH as bcc_tx_hashes_batch's err (the other
+                                    fields are zero then) */
+    unsigned int n_in, n_out, sigops, lock_time;   /* sigops: GetLegacySigOpCount, unscaled */
+    unsigned int stripped_size, total_size;        /* weight = 3 * stripped + total */
+    unsigned char is_coinbase, all_final;          /* all_final: every nSequence is 0xffffffff */
+} bcc_tx_check_result;
+int bcc_tx_check_batch(const bcc_tx_ref* items, size_t n, bcc_tx_check_result* out, int device);
+
+/* (enumerators, not macros: the BCC_BLOCK_* macros above are the commitments entry's eight) */
+enum { BCC_BLOCK_SEGWIT_ACTIVE = 1, BCC_BLOCK_BIP34_ACTIVE = 2 };
+typedef struct bcc_block_check_ref {
+    const unsigned char* block; size_t block_len;
+    int height;                  /* of this block */
+    int64_t lock_time_cutoff;    /* the caller's choice: the median time past of the previous block
+                                    (BIP113) or the block's own time */
+    unsigned int flags;          /* BCC_BLOCK_SEGWIT_ACTIVE | BCC_BLOCK_BIP34_ACTIVE */
+} bcc_block_check_ref;
+typedef struct bcc_block_check_result {
+    int status;                  /* BCC_BLOCK_*: the first rule that applies, in the order below */
+    int tx_index;                /* the transaction BCC_BLOCK_ERR_TX or ERR_NONFINAL names, else -1 */
+    int tx_status;               /* with BCC_BLOCK_ERR_TX: that transaction's BCC_TX_ERR_*; else 0 */
+    unsigned int n_tx;
+    int commit_pos;
+    uint64_t sigops;             /* the sum of GetLegacySigOpCount, unscaled */
+    uint64_t stripped_size;      /* the block without witness data: 80 + the count + the transactions */
+    uint64_t weight;             /* 3 * stripped_size + block_len */
+    unsigned char merkle_root[32], witness_root[32];
+} bcc_block_check_result;
+enum {                                 /* the statuses continue BCC_BLOCK_* above */
+    BCC_BLOCK_ERR_LENGTH = 8,          /* "bad-blk-length" */
+    BCC_BLOCK_ERR_CB_MISSING = 9,      /* "bad-cb-missing" */
+    BCC_BLOCK_ERR_CB_MULTIPLE = 10,    /* "bad-cb-multiple" */
+    BCC_BLOCK_ERR_TX = 11,             /* CheckTransaction refused tx_index with tx_status */
+    BCC_BLOCK_ERR_SIGOPS = 12,         /* "bad-blk-sigops" */
+    BCC_BLOCK_ERR_NONFINAL = 13,       /* "bad-txns-nonfinal" */
+    BCC_BLOCK_ERR_CB_HEIGHT = 14,      /* "bad-cb-height" */
+    BCC_BLOCK_ERR_WEIGHT = 15          /* "bad-blk-weight" */
+};
+/* Per block, Core's order (CheckBlock, then ContextualCheckBlock): deserialize; empty; the merkle
+ * root; the mutation flag; length (n_tx * 4 > 4,000,000 or stripped_size * 4 > 4,000,000); a first
+ * transaction that is no coinbase; a later one that is; the first transaction, in block order, that
+ * CheckTransaction refuses; sigops * 4 > 80,000; the first transaction that is not final at
+ * (height, lock_time_cutoff); with BCC_BLOCK_BIP34_ACTIVE the coinbase scriptSig not starting with
+ * CScript() << height; the three witness-commitment statuses as bcc_block_commitments_batch decides
+ * them; weight > 4,000,000.  n_tx, commit_pos and the roots are that entry's on the same bytes; the
+ * sums are filled for every block with transactions.  One upload serves the hashes and the rules. */
+int bcc_block_check_batch(const bcc_block_check_ref* blocks, size_t n, bcc_block_check_result* out,
+                          int device);
+/* Where the rules' part of the calling thread's last call on one device spent its time, in
+ * milliseconds, summed over its device rounds.  Event times: ms5[0] the transaction lanes, ms5[1]
+ * the duplicate-input lanes, ms5[2] the block lanes (zeros unless BCC_BLOCK_TIMING=1 was in the
+ * environment when the library was loaded).  Host clocks: ms5[3] planning the rounds' rule records,
+ * ms5[4] the long transactions the host evaluated. */
+void bcc_block_rules_last_timing_ms(double* ms5);
+/* For tests: the slot of a table of 2^log2_slots words (1 <= log2_slots <= 31) where the input with
+ * these 36 outpoint bytes in the transaction at row tx_row of its round starts probing, and the
+ * log2_slots a round with `rows` input rows uses (rows: the inputs of its transactions with two or
+ * more inputs). */
+unsigned int bcc_debug_outpoint_slot(unsigned int tx_row, const unsigned char* outpoint36,
+                                     unsigned int log2_slots);
+unsigned int bcc_debug_dup_table_log2(size_t rows);
+
 /* ---- header chains: block hashes, proof of work, retargets ----------------------------------------
  * What CheckBlockHeader and ContextualCheckBlockHeader decide for a run of consecutive 80-byte
  * headers (validation.cpp:3341-3350, 3496-3535): the block hash (SHA-256d of the header),

@@ -1154,6 +1154,131 @@ def block_last_timing_ms(library=None):
     return dict(zip(("txh_kernel", "merkle_kernels", "upload", "download", "parse", "stage"), ms))
 
 
+# ---- a block's transaction rules, sigops, finality, coinbase height, sizes (include/bcc_amd.h) --
+TX_OK = 0
+TX_ERR_VIN_EMPTY = 16
+TX_ERR_VOUT_EMPTY = 17
+TX_ERR_OVERSIZE = 18
+TX_ERR_VOUT_NEGATIVE = 19
+TX_ERR_VOUT_TOOLARGE = 20
+TX_ERR_TXOUTTOTAL_TOOLARGE = 21
+TX_ERR_INPUTS_DUPLICATE = 22
+TX_ERR_CB_LENGTH = 23
+TX_ERR_PREVOUT_NULL = 24
+BLOCK_SEGWIT_ACTIVE = 1
+BLOCK_BIP34_ACTIVE = 2
+BLOCK_ERR_LENGTH = 8
+BLOCK_ERR_CB_MISSING = 9
+BLOCK_ERR_CB_MULTIPLE = 10
+BLOCK_ERR_TX = 11
+BLOCK_ERR_SIGOPS = 12
+BLOCK_ERR_NONFINAL = 13
+BLOCK_ERR_CB_HEIGHT = 14
+BLOCK_ERR_WEIGHT = 15
+
+
+class TxCheckResult(ctypes.Structure):
+    """include/bcc_amd.h bcc_tx_check_result."""
+    _fields_ = [("status", ctypes.c_int), ("n_in", ctypes.c_uint), ("n_out", ctypes.c_uint),
+                ("sigops", ctypes.c_uint), ("lock_time", ctypes.c_uint),
+                ("stripped_size", ctypes.c_uint), ("total_size", ctypes.c_uint),
+                ("is_coinbase", ctypes.c_ubyte), ("all_final", ctypes.c_ubyte)]
+
+
+class BlockCheckRef(ctypes.Structure):
+    """include/bcc_amd.h bcc_block_check_ref."""
+    _fields_ = [("block", ctypes.c_char_p), ("block_len", ctypes.c_size_t), ("height", ctypes.c_int),
+                ("lock_time_cutoff", ctypes.c_int64), ("flags", ctypes.c_uint)]
+
+
+class BlockCheckResult(ctypes.Structure):
+    """include/bcc_amd.h bcc_block_check_result."""
+    _fields_ = [("status", ctypes.c_int), ("tx_index", ctypes.c_int), ("tx_status", ctypes.c_int),
+                ("n_tx", ctypes.c_uint), ("commit_pos", ctypes.c_int), ("sigops", ctypes.c_uint64),
+                ("stripped_size", ctypes.c_uint64), ("weight", ctypes.c_uint64),
+                ("merkle_root", ctypes.c_ubyte * 32), ("witness_root", ctypes.c_ubyte * 32)]
+
+
+def _bind_block_rules(L):
+    _bind_block(L)
+    if getattr(L, "_bcc_block_rules_bound", False):
+        return L
+    L.bcc_tx_check_batch.argtypes = [ctypes.POINTER(TxRef), ctypes.c_size_t,
+                                     ctypes.POINTER(TxCheckResult), ctypes.c_int]
+    L.bcc_block_check_batch.argtypes = [ctypes.POINTER(BlockCheckRef), ctypes.c_size_t,
+                                        ctypes.POINTER(BlockCheckResult), ctypes.c_int]
+    L.bcc_block_rules_last_timing_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.bcc_block_rules_last_timing_ms.restype = None
+    L.bcc_debug_outpoint_slot.argtypes = [ctypes.c_uint, ctypes.c_char_p, ctypes.c_uint]
+    L.bcc_debug_outpoint_slot.restype = ctypes.c_uint
+    L.bcc_debug_dup_table_log2.argtypes = [ctypes.c_size_t]
+    L.bcc_debug_dup_table_log2.restype = ctypes.c_uint
+    L._bcc_block_rules_bound = True
+    return L
+
+
+def tx_check_batch(txs, device=0, library=None):
+    """bcc_tx_check_batch: CheckTransaction and the legacy sigop count of each serialized
+    transaction.  Returns one dict per item: status (TX_OK, a TX_ERR_*, or the crate's
+    ERR_TX_DESERIALIZE / ERR_TX_SIZE_MISMATCH, with every other field zero), n_in, n_out, sigops,
+    lock_time, stripped_size, total_size, is_coinbase, all_final."""
+    n = len(txs)
+    keep = [bytes(t) for t in txs]
+    arr = (TxRef * max(n, 1))()
+    for i, t in enumerate(keep):
+        arr[i] = TxRef(t, len(t))
+    res = (TxCheckResult * max(n, 1))()
+    L = _bind_block_rules(library if library is not None else lib())
+    rc = L.bcc_tx_check_batch(arr, n, res, device)
+    if rc != 0:
+        raise RuntimeError(f"bcc_tx_check_batch failed: {rc}")
+    return [{k: getattr(res[i], k) for k, _ in TxCheckResult._fields_} for i in range(n)]
+
+
+def block_check_batch(blocks, device=0, library=None):
+    """bcc_block_check_batch.  blocks: [(raw block bytes, height, lock_time_cutoff, flags)], flags of
+    BLOCK_SEGWIT_ACTIVE | BLOCK_BIP34_ACTIVE.  Returns one dict per block: status (BLOCK_*, the first
+    rule that applies in Core's order), tx_index, tx_status, n_tx, commit_pos, sigops, stripped_size,
+    weight, merkle_root, witness_root."""
+    n = len(blocks)
+    keep = [bytes(b[0]) for b in blocks]
+    arr = (BlockCheckRef * max(n, 1))()
+    for i, raw in enumerate(keep):
+        arr[i] = BlockCheckRef(raw, len(raw), blocks[i][1], blocks[i][2], blocks[i][3])
+    res = (BlockCheckResult * max(n, 1))()
+    L = _bind_block_rules(library if library is not None else lib())
+    rc = L.bcc_block_check_batch(arr, n, res, device)
+    if rc != 0:
+        raise RuntimeError(f"bcc_block_check_batch failed: {rc}")
+    out = []
+    for i in range(n):
+        d = {k: getattr(res[i], k) for k, _ in BlockCheckResult._fields_}
+        d["merkle_root"], d["witness_root"] = bytes(res[i].merkle_root), bytes(res[i].witness_root)
+        out.append(d)
+    return out
+
+
+def block_rules_last_timing_ms(library=None):
+    """bcc_block_rules_last_timing_ms: event times of the rule kernels in the calling thread's last
+    call (zeros unless BCC_BLOCK_TIMING=1 was set when the library was loaded), then host clocks of
+    the rounds' planning and of the long transactions evaluated on the host."""
+    ms = (ctypes.c_double * 5)()
+    _bind_block_rules(library if library is not None else lib()).bcc_block_rules_last_timing_ms(ms)
+    return dict(zip(("tx_rules_kernel", "dup_input_kernel", "block_rules_kernel", "host_plan", "host_long_txs"), ms))
+
+
+def debug_outpoint_slot(tx_row, outpoint36, log2_slots, library=None):
+    """bcc_debug_outpoint_slot: where this input starts probing the duplicate table."""
+    assert len(outpoint36) == 36
+    L = _bind_block_rules(library if library is not None else lib())
+    return L.bcc_debug_outpoint_slot(tx_row, bytes(outpoint36), log2_slots)
+
+
+def debug_dup_table_log2(rows, library=None):
+    """bcc_debug_dup_table_log2: log2 of the duplicate table's slots for a round of `rows` rows."""
+    return _bind_block_rules(library if library is not None else lib()).bcc_debug_dup_table_log2(rows)
+
+
 # ---- header chains: block hashes, proof of work, retargets (include/bcc_amd.h) -----------------
 HEADER_OK = 0
 HEADER_HIGH_HASH = 1

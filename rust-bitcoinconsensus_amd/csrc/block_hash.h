@@ -156,6 +156,7 @@ SHA_HD bool merkle_lane_run(const MerkleLane& L) {
 // item that does not parse); rounds with trees have a job for every row.  segs: level 0's trees
 // over the node rows, each with the index of its root row and mutation word (the rows of trees no
 // seg names keep what the caller wrote).
+struct BlockRulesRound;  // block_rules.h
 struct BlockRound {
     const TxHashJob* jobs = nullptr;
     const uint8_t* const* src = nullptr;
@@ -172,6 +173,8 @@ struct BlockRound {
     uint8_t* wtxid = nullptr;
     uint8_t* roots = nullptr;
     uint32_t* mut = nullptr;
+    // the transaction and block rules over the same jobs (block_rules.h); null: hashes only
+    BlockRulesRound* rules = nullptr;
     // counted by whoever runs the round
     size_t long_txs = 0, merkle_launches = 0;
     size_t node_rows() const { return leaves ? n_leaves : 2 * rows; }

@@ -24,6 +24,7 @@
 //                                  buffers; a tree's last parent goes to its root row.
 // The host half lives here rather than under csrc/host because it launches kernels.
 #include "block_hash.h"
+#include "block_rules.h"
 #include "gpu_common.h"
 #include "host/hashes.h"
 #include "host/tuples.h"
@@ -149,11 +150,16 @@ int block_round(int device, BlockRound& r) {
     if (!merkle_levels(r.segs, nseg, T.table, T.level, T.level_lanes)) return (int)hipErrorInvalidValue;
     const size_t nl = T.lanes.size(), nlate = T.late.size(), nlev = T.level_lanes.size();
 
-    // uploaded: raw | jobs | lanes | tables | mutation words (zero);  then, uploaded behind K_txh:
-    // late rows | late digests;  downloaded with the mutation words: roots | node rows;  device
-    // only: the two level buffers
-    enum { RAW, JOBS, LANES, TAB, MUT, UPLOADED, LATE = UPLOADED, LATED, ROOTS, NODES, HOSTED,
-           LVA = HOSTED, LVB, NB };
+    // the rules that ride on the round (block_rules.hip): their records are checked here too
+    const BlockRulesDeviceHook* rules = r.rules ? g_block_rules_device_hook : nullptr;
+    BlockRulesPlan rp;
+    if (r.rules && (!rules || rules->plan(r, rp) != 0)) return (int)hipErrorInvalidValue;
+
+    // uploaded: raw | jobs | lanes | tables | mutation words (zero) | the rules' records;  then,
+    // uploaded behind K_txh: late rows | late digests;  downloaded with the mutation words: roots |
+    // node rows;  the rules' page-locked region;  device only: the two level buffers, the rules'
+    enum { RAW, JOBS, LANES, TAB, MUT, RUP, UPLOADED, LATE = UPLOADED, LATED, ROOTS, NODES, RHOST,
+           HOSTED, LVA = HOSTED, LVB, RDEV, NB };
     size_t sizes[NB] = {}, off[NB + 1];
     sizes[RAW] = n ? r.raw_bytes + 4 : 0;  // (xs_put loads whole dwords)
     sizes[JOBS] = sizeof(TxHashJob) * n;
@@ -166,6 +172,9 @@ int block_round(int device, BlockRound& r) {
     sizes[NODES] = 32 * NR;
     sizes[LVA] = nlev > 1 ? 32 * NR : 0;  // (the last level writes roots only)
     sizes[LVB] = nlev > 2 ? 32 * NR : 0;
+    sizes[RUP] = rp.up_bytes;
+    sizes[RHOST] = rp.host_bytes;
+    sizes[RDEV] = rp.dev_bytes;
     const size_t total = arena_layout(sizes, off, NB);
     void *dv = nullptr, *hv = nullptr, *sv = nullptr;
     if (int e = tuple_thread_buffers(device, total, off[HOSTED], &dv, &hv, &sv)) return e;
@@ -181,6 +190,7 @@ int block_round(int device, BlockRound& r) {
     if (nl) memcpy(h + off[LANES], T.lanes.data(), 4 * nl);
     if (!T.table.empty()) memcpy(h + off[TAB], T.table.data(), sizeof(MerkleSeg) * T.table.size());
     memset(h + off[MUT], 0, 4 * nt);
+    if (rules) rules->fill(r, h + off[RUP]);
 
     tl_kernel_ms[BLOCK_MS_STAGE] +=
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - stage0).count();
@@ -203,6 +213,11 @@ int block_round(int device, BlockRound& r) {
                            (const uint32_t*)(d + off[LANES]), (uint32_t)nl, d_nodes, d_nodes + 32 * rows);
         kt.end();
         BCC_HIP_TRY(hipGetLastError());
+    }
+    if (rules) {  // behind the upload, beside K_txh; its long transactions on the host meanwhile
+        if (int e = rules->launch(r, st, d + off[RAW], (const TxHashJob*)(d + off[JOBS]), d + off[RUP],
+                                  h + off[RHOST], d + off[RHOST], d + off[RDEV]))
+            return e;
     }
     if (nlate) {  // the long chains, on the host while K_txh runs
         uint32_t* lr = (uint32_t*)(h + off[LATE]);
@@ -251,6 +266,7 @@ int block_round(int device, BlockRound& r) {
     kt.end();
     BCC_HIP_TRY(hipStreamSynchronize(st));
     kt.collect();
+    if (rules) rules->collect(r, h + off[RHOST]);
     for (size_t s = 0; s < nseg; s++) {  // (a tree no seg names keeps the caller's row)
         const size_t t = r.segs[s].seg;
         if (r.segs[s].n_in == 0) continue;

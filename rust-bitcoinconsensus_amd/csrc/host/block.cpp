@@ -19,8 +19,10 @@
 #include <vector>
 
 #include "../block_hash.h"
+#include "../block_rules.h"
 #include "bcc_amd.h"
 #include "bitcoinconsensus.h"
+#include "block_entry.h"
 #include "devices.h"
 #include "engine.h"
 #include "hashes.h"
@@ -73,6 +75,7 @@ thread_local double t_parse_ms = 0;  // bcc_block_last_timing_ms: the calling th
 void reset_timing() {
     t_parse_ms = 0;
     if (g_block_device_hook) g_block_device_hook->timing_ms(nullptr, 1);
+    if (g_block_rules_device_hook) g_block_rules_device_hook->timing_ms(nullptr, 1);
 }
 struct ParseClock {  // adds its lifetime to the calling thread's parse time
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -149,6 +152,7 @@ struct ParsedBlock {
     const uint8_t* nonce32 = nullptr;   // the reserved value
     size_t bytes = 0;                   // message bytes of its digests and trees
     std::vector<TxHashJob> jobs;        // off from the block's first byte, row = tx index
+    std::vector<uint32_t> n_in;         // the rule entries: each transaction's input count
     void reset(int st) {  // (jobs keeps its capacity from call to call)
         status = st;
         commit_pos = -1;
@@ -156,10 +160,11 @@ struct ParsedBlock {
         commit32 = nonce32 = nullptr;
         bytes = 0;
         jobs.clear();
+        n_in.clear();
     }
 };
 
-void parse_block(const bcc_block_ref& b, ParsedBlock& P, Tx& tx) {
+void parse_block(const bcc_block_ref& b, ParsedBlock& P, Tx& tx, bool rules) {
     P.reset(BCC_BLOCK_ERR_DESERIALIZE);
     const uint8_t* p = b.block;
     const size_t len = b.block_len;
@@ -191,6 +196,7 @@ void parse_block(const bcc_block_ref& b, ParsedBlock& P, Tx& tx) {
             }
         }
         P.jobs.push_back(j);
+        if (rules) P.n_in.push_back((uint32_t)tx.vin.size());
         pos += tx.ser_size;
     }
     if (pos != len) {
@@ -222,7 +228,15 @@ struct RoundState {
     std::vector<uint8_t> txid, roots;
     std::vector<uint32_t> mut;
     std::vector<uint8_t> rows;  // block_round_host's node rows
+    // the rule entries: input table rows per job (prefix sums), the blocks' contexts and results,
+    // the jobs' records
+    std::vector<uint32_t> in_base;
+    std::vector<BlockRuleCtx> ctx;
+    std::vector<BlockRuleOut> rule_out;
+    std::vector<TxRuleRec> recs;
 };
+// rows of the input table: a transaction with one input cannot repeat an outpoint
+uint32_t in_rows(uint32_t n_in) { return n_in >= 2 ? n_in : 0; }
 thread_local RoundState tl_round;
 thread_local std::vector<ParsedBlock> tl_blocks;
 
@@ -235,7 +249,10 @@ struct RangeState {
 // The round under the failure rules: on the host when it is small or cannot be indexed by the
 // device records, else on the device with one retry and the policy.
 int run_round(const char* who, BlockRound& r, size_t rows, bool device_ok, RangeState& rs) {
-    auto on_host = [&] { block_round_host(r, host_threads()); };
+    auto on_host = [&] {
+        block_round_host(r, host_threads());
+        if (r.rules) block_rules_round_host(r);
+    };
     if (!device_ok || rows <= block_small_round()) {
         on_host();
         rs.c.t.round(rows, 0, true);
@@ -255,7 +272,7 @@ int run_round(const char* who, BlockRound& r, size_t rows, bool device_ok, Range
 
 // Blocks [lo, hi) of one device range, in rounds of whole blocks.
 int blocks_range(const bcc_block_ref* blocks, const ParsedBlock* parsed, size_t lo, size_t hi,
-                 bcc_block_result* out, RangeState& rs) {
+                 bcc_block_result* out, RangeState& rs, const BlockRulesCall* rules) {
     RoundState& S = tl_round;
     const size_t round_txs = block_round_txs();
     for (size_t b0 = lo; b0 < hi;) {
@@ -274,6 +291,8 @@ int blocks_range(const bcc_block_ref* blocks, const ParsedBlock* parsed, size_t 
         S.txid.resize(32 * n);
         S.roots.assign(64 * (b1 - b0), 0);
         S.mut.assign(2 * (b1 - b0), 0);
+        S.ctx.clear();
+        if (rules) S.in_base.assign(n + 1, 0);
         size_t row0 = 0, raw0 = 0;
         for (size_t b = b0; b < b1; b++) {
             const ParsedBlock& P = parsed[b];
@@ -284,6 +303,15 @@ int blocks_range(const bcc_block_ref* blocks, const ParsedBlock* parsed, size_t 
             const uint32_t t = (uint32_t)(2 * (b - b0));
             S.segs.push_back(MerkleSeg{(uint32_t)row0, (uint32_t)bn, 0, t});
             if (P.nonce_ok) S.segs.push_back(MerkleSeg{(uint32_t)(n + row0), (uint32_t)bn, 0, t + 1});
+            if (rules) {
+                BlockRuleCtx c = rules->ctx(b);
+                c.job0 = 0;
+                c.n_tx = (uint32_t)bn;
+                rebase(c, BlockRuleBase{(uint32_t)row0});
+                S.ctx.push_back(c);
+                for (size_t k = 0; k < bn; k++)
+                    S.in_base[row0 + k + 1] = S.in_base[row0 + k] + in_rows(P.n_in[k]);
+            }
             row0 += bn;
             raw0 += blocks[b].block_len;
         }
@@ -300,10 +328,22 @@ int blocks_range(const bcc_block_ref* blocks, const ParsedBlock* parsed, size_t 
             r.txid = S.txid.data();
             r.roots = S.roots.data();
             r.mut = S.mut.data();
-            if (int e = run_round("block_commitments_batch", r, n, raw < BLOCK_MAX_BYTES, rs)) return e;
+            BlockRulesRound q;
+            if (rules) {
+                S.rule_out.assign(S.ctx.size(), BlockRuleOut{});
+                q.in_base = S.in_base.data();
+                q.ctx = S.ctx.data();
+                q.n_blocks = S.ctx.size();
+                q.out = S.rule_out.data();
+                r.rules = &q;
+            }
+            if (int e = run_round(rules ? "block_check_batch" : "block_commitments_batch", r, n,
+                                  raw < BLOCK_MAX_BYTES, rs))
+                return e;
         }
         // the comparisons, in Core's order
         row0 = 0;
+        size_t kb = 0;  // the blocks of the round that have transactions
         for (size_t b = b0; b < b1; b++) {
             const ParsedBlock& P = parsed[b];
             bcc_block_result& R = out[b];
@@ -311,7 +351,10 @@ int blocks_range(const bcc_block_ref* blocks, const ParsedBlock* parsed, size_t 
             R.status = P.status;
             R.commit_pos = -1;
             rs.c.blocks++;
-            if (P.status) continue;
+            if (P.status) {
+                if (rules) rules->block(b, R, nullptr);
+                continue;
+            }
             const size_t bn = P.jobs.size();
             const uint8_t* root = &S.roots[64 * (b - b0)];
             R.n_tx = (unsigned)bn;
@@ -340,6 +383,7 @@ int blocks_range(const bcc_block_ref* blocks, const ParsedBlock* parsed, size_t 
             } else if (P.any_witness) {
                 R.status = BCC_BLOCK_ERR_UNEXPECTED_WITNESS;
             }
+            if (rules) rules->block(b, R, &S.rule_out[kb++]);
         }
         b0 = b1;
     }
@@ -351,12 +395,13 @@ int blocks_range(const bcc_block_ref* blocks, const ParsedBlock* parsed, size_t 
 struct TxPart {
     std::vector<TxHashJob> jobs;
     std::vector<const uint8_t*> src;
+    std::vector<uint32_t> n_in;  // the rule entries: each job's input count
     size_t raw = 0;
 };
 thread_local std::vector<TxPart> tl_tx_parts;
 
 int tx_range(const bcc_tx_ref* items, size_t lo, size_t hi, uint8_t* txid_out, uint8_t* wtxid_out,
-             int* err_out, RangeState& rs) {
+             int* err_out, RangeState& rs, const BlockRulesCall* rules) {
     RoundState& S = tl_round;
     const size_t round_txs = block_round_txs();
     for (size_t r0 = lo; r0 < hi;) {
@@ -372,6 +417,7 @@ int tx_range(const bcc_tx_ref* items, size_t lo, size_t hi, uint8_t* txid_out, u
             TxPart& P = parts[t];
             P.jobs.clear();
             P.src.clear();
+            P.n_in.clear();
             P.raw = 0;
             Tx tx;
             const size_t a = r0 + m * t / T, b = r0 + m * (t + 1) / T;
@@ -380,6 +426,7 @@ int tx_range(const bcc_tx_ref* items, size_t lo, size_t hi, uint8_t* txid_out, u
                 if (!parse_tx(items[i].tx, items[i].tx_len, tx)) e = bitcoinconsensus_ERR_TX_DESERIALIZE;
                 else if (tx.ser_size != items[i].tx_len) e = bitcoinconsensus_ERR_TX_SIZE_MISMATCH;
                 if (err_out) err_out[i] = e;
+                if (e && rules) rules->tx(i, e, nullptr);
                 if (e) {  // no record: the rows stay zero
                     if (txid_out) memset(txid_out + 32 * i, 0, 32);
                     if (wtxid_out) memset(wtxid_out + 32 * i, 0, 32);
@@ -390,6 +437,7 @@ int tx_range(const bcc_tx_ref* items, size_t lo, size_t hi, uint8_t* txid_out, u
                 j.flags = wtxid_out ? TXH_W : 0;
                 P.jobs.push_back(j);
                 P.src.push_back(items[i].tx);
+                if (rules) P.n_in.push_back((uint32_t)tx.vin.size());
                 P.raw += items[i].tx_len;
             }
         });
@@ -399,8 +447,11 @@ int tx_range(const bcc_tx_ref* items, size_t lo, size_t hi, uint8_t* txid_out, u
         S.jobs.resize(n);
         S.src.resize(n);
         size_t k0 = 0, raw0 = 0, bytes = 0;
+        if (rules) S.in_base.assign(n + 1, 0);
         for (unsigned t = 0; t < T; t++) {
             const TxPart& P = parts[t];
+            for (size_t k = 0; rules && k < P.jobs.size(); k++)
+                S.in_base[k0 + k + 1] = S.in_base[k0 + k] + in_rows(P.n_in[k]);
             rebase_copy(S.jobs.data() + k0, P.jobs.data(), P.jobs.size(),
                         BlockBase{(uint32_t)raw0, (uint32_t)(m * t / T)});
             std::copy(P.src.begin(), P.src.end(), S.src.begin() + k0);
@@ -420,7 +471,17 @@ int tx_range(const bcc_tx_ref* items, size_t lo, size_t hi, uint8_t* txid_out, u
             S.txid.resize(32 * m);
             r.txid = txid_out ? txid_out + 32 * r0 : S.txid.data();
             r.wtxid = wtxid_out ? wtxid_out + 32 * r0 : nullptr;
-            if (int e = run_round("tx_hashes_batch", r, n, raw0 < BLOCK_MAX_BYTES, rs)) return e;
+            BlockRulesRound q;
+            if (rules) {
+                S.recs.assign(n, TxRuleRec{});
+                q.in_base = S.in_base.data();
+                q.recs = S.recs.data();
+                r.rules = &q;
+            }
+            if (int e = run_round(rules ? "tx_check_batch" : "tx_hashes_batch", r, n,
+                                  raw0 < BLOCK_MAX_BYTES, rs))
+                return e;
+            for (size_t k = 0; rules && k < n; k++) rules->tx(r0 + S.jobs[k].row, 0, &S.recs[k]);
         }
         rs.c.txs += n;
         rs.c.bytes += bytes;
@@ -554,10 +615,11 @@ void block_release_thread_state() {
 using namespace bcc;
 using namespace bcc::host;
 
-extern "C" {
+namespace bcc {
+namespace host {
 
-int bcc_tx_hashes_batch(const bcc_tx_ref* items, size_t n, unsigned char* txid_out,
-                        unsigned char* wtxid_out, int* err_out, int device) {
+int block_entry_txs(const bcc_tx_ref* items, size_t n, uint8_t* txid_out, uint8_t* wtxid_out,
+                    int* err_out, int device, const BlockRulesCall* rules) {
     if (n == 0) return 0;
     if (!items) return -1;
     for (size_t i = 0; i < n; i++)
@@ -566,10 +628,48 @@ int bcc_tx_hashes_batch(const bcc_tx_ref* items, size_t n, unsigned char* txid_o
     BlockCounters c;
     const int rc = over_devices(device, std::vector<size_t>(n, 1), [&](int dev, size_t lo, size_t hi) {
         RangeState rs{dev, {}, c};
-        return tx_range(items, lo, hi, txid_out, wtxid_out, err_out, rs);
+        return tx_range(items, lo, hi, txid_out, wtxid_out, err_out, rs, rules);
     });
     c.store();
     return rc ? -1 : 0;
+}
+
+int block_entry_blocks(const bcc_block_ref* blocks, size_t n, bcc_block_result* out, int device,
+                       const BlockRulesCall* rules) {
+    if (n == 0) return 0;
+    if (!blocks || !out) return -1;
+    for (size_t i = 0; i < n; i++)
+        if (!blocks[i].block) return -1;
+    reset_timing();
+    std::vector<ParsedBlock>& parsed = tl_blocks;
+    if (parsed.size() < n) parsed.resize(n);
+    {
+        ParseClock clock;
+        pfor(n, 1, [&](size_t lo, size_t hi) {
+            Tx tx;
+            for (size_t b = lo; b < hi; b++) parse_block(blocks[b], parsed[b], tx, rules != nullptr);
+        });
+    }
+    std::vector<size_t> weight(n);
+    for (size_t b = 0; b < n; b++) weight[b] = parsed[b].jobs.size() + 1;
+    BlockCounters c;
+    const ParsedBlock* pb = parsed.data();
+    const int rc = over_devices(device, weight, [&](int dev, size_t lo, size_t hi) {
+        RangeState rs{dev, {}, c};
+        return blocks_range(blocks, pb, lo, hi, out, rs, rules);
+    });
+    c.store();
+    return rc ? -1 : 0;
+}
+
+}  // namespace host
+}  // namespace bcc
+
+extern "C" {
+
+int bcc_tx_hashes_batch(const bcc_tx_ref* items, size_t n, unsigned char* txid_out,
+                        unsigned char* wtxid_out, int* err_out, int device) {
+    return block_entry_txs(items, n, txid_out, wtxid_out, err_out, device, nullptr);
 }
 
 int bcc_merkle_root(const unsigned char* leaves32, size_t n, unsigned char* root32, int* mutated,
@@ -607,30 +707,7 @@ int bcc_merkle_root(const unsigned char* leaves32, size_t n, unsigned char* root
 
 int bcc_block_commitments_batch(const bcc_block_ref* blocks, size_t n, bcc_block_result* out,
                                 int device) {
-    if (n == 0) return 0;
-    if (!blocks || !out) return -1;
-    for (size_t i = 0; i < n; i++)
-        if (!blocks[i].block) return -1;
-    reset_timing();
-    std::vector<ParsedBlock>& parsed = tl_blocks;
-    if (parsed.size() < n) parsed.resize(n);
-    {
-        ParseClock clock;
-        pfor(n, 1, [&](size_t lo, size_t hi) {
-            Tx tx;
-            for (size_t b = lo; b < hi; b++) parse_block(blocks[b], parsed[b], tx);
-        });
-    }
-    std::vector<size_t> weight(n);
-    for (size_t b = 0; b < n; b++) weight[b] = parsed[b].jobs.size() + 1;
-    BlockCounters c;
-    const ParsedBlock* pb = parsed.data();
-    const int rc = over_devices(device, weight, [&](int dev, size_t lo, size_t hi) {
-        RangeState rs{dev, {}, c};
-        return blocks_range(blocks, pb, lo, hi, out, rs);
-    });
-    c.store();
-    return rc ? -1 : 0;
+    return block_entry_blocks(blocks, n, out, device, nullptr);
 }
 
 void bcc_last_block_stats(bcc_block_stats* out) {
